@@ -16,10 +16,23 @@ GPU over RCCL); under torchrun it reads RANK / LOCAL_RANK / WORLD_SIZE and check
 Every rank owns a disjoint shard of the offline dataset (its own replay buffer), the per-rank batch
 stays 65536 (weak scaling) and the only collective is the gradient all-reduce.
 
-Prints ONE JSON line (rank 0), at most LINE_LIMIT = 4096 bytes: the contract's keys + `roofline` + `cpu_baseline` + digests of
-`parity`, of the 1e-4-compliant bf16x3 mode (`compliant`, the co-headline) and of the other single-GPU configurations (`c3`,
-`c4`) — see compact_line().  The FULL record (every object below, every digit) goes to bench_report.json (--report).
-Objects of the full record:
+A plain run (`--gpus 1 --steps K --warmup W`) does what its headline figure needs and nothing else: it builds the workload,
+warms up, times ONE region of exactly K steps (`ms_per_step` = that region's time / K), writes the last step's outputs when
+`--dump-outputs DIR` is given, and prints the line.  `--full` adds everything else the benchmark measures or checks: the
+device preflight, the parity step, the sustained region, the instrumented pass (`roofline`), the 1e-4-compliant bf16x3
+region, the C3 / C4 regions, the CPU baseline and the report file.
+
+`--dump-outputs DIR`: after the timed region, what the timed step handed its caller in its LAST step — the loss(es), the
+batch's Q-values where the trainer keeps them, every floating-point tensor of the trainer's state (networks and targets
+after Adam + soft update) — as DIR/<name>.npy in float32, at most DUMP_LIMIT bytes in all.  Inputs are seeded (replay
+shard, initial weights, normalisation table, the device generator the index draws come from): the same arguments give the
+same inputs on every run, so two builds can be compared output for output.
+
+Prints ONE JSON line (rank 0), at most LINE_LIMIT = 4096 bytes: the contract's keys, and under --full `roofline` +
+`cpu_baseline` + digests of `parity`, of the 1e-4-compliant bf16x3 mode (`compliant`, the co-headline) and of the other
+single-GPU configurations (`c3`, `c4`) — see compact_line().  Under --full the FULL record (every object below, every digit)
+goes to bench_report.json (--report).
+Objects of the full record (--full):
   roofline     — dominant FC entry point (largest total time, all its variants merged, call-weighted):
                  algorithmic FLOP of its launches / HIP-event time of those launches (events on the launch
                  stream, in a second, instrumented pass so the timed region itself stays un-instrumented;
@@ -51,6 +64,7 @@ MFMA_PEAK = {"bf16": 2.5e15, "bf16x3": 2.5e15, "f32": 157.3e12}  # /opt/skills/g
 HBM_PEAK = 8.0e12
 LINE_LIMIT = 4096  # bytes of the ONE line rank 0 prints (round 5's 35.5 KB line was not parsed by the driver)
 REPORT_FILE = "bench_report.json"
+DUMP_LIMIT = 64 << 20  # bytes of all --dump-outputs files together
 
 CONFIGS = {
     "c2": dict(algo="dqn", state_dim=128, actions=16, atoms=None,
@@ -165,7 +179,14 @@ def parse():
     ap.add_argument("--layers", type=int, default=3)
     ap.add_argument("--capacity", type=int, default=1 << 20)
     ap.add_argument("--precision", choices=["bf16", "bf16x3", "f32"], default="bf16")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps; the median one is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="timed regions of --steps steps; the median one is reported (default 1: exactly --steps timed steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything besides the headline: device preflight, parity step, sustained region, "
+                         "instrumented pass, bf16x3 region, C3 / C4 regions, CPU baseline, report file (the --no-* flags "
+                         "below and --sustained-steps then pick among them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-profile", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -181,12 +202,15 @@ def parse():
     ap.add_argument("--graph-steps", type=int, default=1,
                     help="consecutive steps recorded per HIP graph where the loop supports it (must divide --steps); measured round 4 at 1 / 2 / 4 / 8: 0.5125 / 0.5134 / 0.5126 / 0.5159 ms per C2 step — no gain, default 1")
     ap.add_argument("--sustained-steps", type=int, default=4000,
-                    help="steps of the one long region reported as `sustained` next to the K-step regions (0: skip)")
+                    help="--full: steps of the one long region reported as `sustained` next to the K-step regions (0: skip)")
     ap.add_argument("--report", default=None, help=f"where the full record goes (default {REPORT_FILE} beside bench.py); the printed "
                                                    "line is a digest of it, at most LINE_LIMIT bytes")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="launcher self-test: form the process group (gloo when there is no GPU), report its size, exit")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline region alone (module docstring)
+        args.no_cpu_baseline = args.no_kernel_profile = args.no_parity = args.no_accurate = args.no_also = True
+        args.sustained_steps = 0
     c = CONFIGS[args.config]
     if args.gpus is None:
         args.gpus = 8 if args.config == "c5" else 1
@@ -832,9 +856,10 @@ def kernel_profile(args, step, steps, device=None, gpu_ms=None):
     return out
 
 
-def measure(args, device, rank, world, dist, cols=None, profile_steps=None):
+def measure(args, device, rank, world, dist, cols=None, profile_steps=None, dump_dir=None):
     """build the workload `args` names on this rank, run the parity step, pick the launch path, time `--repeats` regions
-    of exactly `--steps` steps, run the instrumented pass; returns the numbers (all ranks) for rank 0 to print"""
+    of exactly `--steps` steps (rank 0 writes the last step's outputs to `dump_dir`), run the instrumented pass; returns
+    the numbers (all ranks) for rank 0 to print"""
     loop, trainer, init, cols, norm = build(args, device, rank, cols=cols)
     if args.algo == "qrdqn":
         from reagent_amd.qr_engine import GroupedQR
@@ -979,6 +1004,8 @@ def measure(args, device, rank, world, dist, cols=None, profile_steps=None):
     order = sorted(range(len(regions)), key=lambda i: regions[i])
     mid = order[len(order) // 2]
     dt, host_dt = regions[mid], host_regions[mid]
+    if dump_dir and rank == 0:  # before any further step (sustained region, instrumented pass) moves the state on
+        dump_outputs(dump_dir, step_outputs(trainer, loss))
     if isinstance(loss, dict):
         loss = loss["q1_loss"]
     loss_val = float(loss.item())
@@ -1029,7 +1056,7 @@ def measure(args, device, rank, world, dist, cols=None, profile_steps=None):
         per_rank = [{"rank": i, "ms_per_step": t[0].item(), "host_enqueue_ms_per_step": t[1].item(),
                      "all_reduce_us": t[2].item(), "cpus_in_affinity": t[3].item()} for i, t in enumerate(allr)]
     return {"value": world * args.batch * args.steps / dt, "ms_per_step": dt / args.steps * 1e3,
-            "timing": f"median of {len(regions)} regions of {args.steps} steps each",
+            "timing": (f"median of {len(regions)} regions" if len(regions) > 1 else "one region") + f" of {args.steps} steps",
             "region_ms": [round(r * 1e3, 4) for r in regions], "host_enqueue_ms_per_step": host_dt / args.steps * 1e3,
             "final_loss": loss_val, "launch": (graph_note or "eager launches"), "launch_calibration": calibration,
             "sustained": sustained, "extra": extra, "parity": parity,
@@ -1182,6 +1209,45 @@ def write_report(res, path=None):
     return written
 
 
+def step_outputs(trainer, out):
+    """What a caller of the timed step holds after its last step: what the step returned (the loss; SAC: its dict of losses
+    and statistics), the batch's Q-values where the trainer keeps them, and every floating-point tensor of the trainer's
+    state (the networks and their targets after Adam + soft update)."""
+    arrays = {}
+    for k, v in (out.items() if isinstance(out, dict) else [("loss", out)]):
+        if isinstance(v, torch.Tensor) and v.is_floating_point():
+            arrays[k if k == "loss" else f"step.{k}"] = v
+    q = getattr(trainer, "all_action_scores", None)
+    if isinstance(q, torch.Tensor):
+        arrays["q_values"] = q
+    for k, v in trainer.state_dict().items():
+        if isinstance(v, torch.Tensor) and v.is_floating_point():
+            arrays[f"state.{k}"] = v
+    return arrays
+
+
+def dump_outputs(directory, arrays, limit=DUMP_LIMIT):
+    """arrays -> directory/<name>.npy in float32.  Over `limit` bytes in all, the largest arrays are replaced, largest first,
+    by a fixed sample of their elements (flattened; positions drawn with seed 0, in ascending order) until the set fits."""
+    import re
+
+    import numpy as np
+
+    host = {re.sub(r"[^A-Za-z0-9_.-]", "_", k): v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for k in sorted(host, key=lambda k: -host[k].nbytes):
+        if total <= limit:
+            break
+        a = host[k].reshape(-1)
+        keep = max(1, a.size - -(-(total - limit) // a.itemsize))
+        host[k] = a[np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))]
+        total -= a.nbytes - host[k].nbytes
+    os.makedirs(directory, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(directory, k + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(host)
+
+
 def main(device=None, backend="nccl"):
     """`device` / `backend` are None / "nccl" for every real run.  tests/bench_on_emu.py passes (cpu, "gloo") AFTER patching the
     C ABI to the host-compiled kernel sources, to run this function's whole control flow — launcher, ranks, secondary regions,
@@ -1198,7 +1264,8 @@ def main(device=None, backend="nccl"):
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
     preflight = None
-    if device is None and world == 1 and os.path.exists("/dev/kfd") and not args.rendezvous_only and not os.environ.get("RG_SKIP_PREFLIGHT"):
+    if (args.full and device is None and world == 1 and os.path.exists("/dev/kfd") and not args.rendezvous_only
+            and not os.environ.get("RG_SKIP_PREFLIGHT")):
         # One GPU: the torch-only first device touch in a SUBPROCESS, before this process starts its HSA runtime (so before
         # torch.cuda.is_available()).  A lease whose first touch faults (round 4's driver GPU record died that way) is tried
         # under the runtime alternatives of reagent_amd.device_preflight and named if none works: the record then blames the
@@ -1243,7 +1310,8 @@ def main(device=None, backend="nccl"):
         else:
             dist.init_process_group(backend)
         assert dist.get_world_size() == args.gpus
-    m = measure(args, device, rank, world, dist)
+    torch.manual_seed(0)  # the device generator the index draws come from: the same inputs on every run
+    m = measure(args, device, rank, world, dist, dump_dir=args.dump_outputs)
     if dist is not None:
         dist.barrier()
     if rank == 0:
@@ -1343,7 +1411,7 @@ def main(device=None, backend="nccl"):
                 res["cpu_baseline"] = cpu_baseline(args, m["init"], m["cols_cpu"], m["norm"])
             except Exception as e:  # the baseline must never take the GPU number down with it
                 res["cpu_baseline"] = {"error": repr(e)}
-        where = write_report(res, args.report)
+        where = write_report(res, args.report) if (args.full or args.report) else None
         res["report_file"] = os.path.relpath(where, ROOT) if where else None
         sys.stderr.flush()
         print(compact_line(res), flush=True)

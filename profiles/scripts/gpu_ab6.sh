@@ -9,7 +9,7 @@ CFG=${AB_CONFIG:-c2}; PREC=${AB_PREC:-bf16}
 for rep in $(seq 1 ${AB_REPS:-2}); do
 for envs in "$@"; do
   [ "$envs" = "-" ] && envs="RG_NONE=1"
-  env $envs RG_SKIP_PREFLIGHT=1 timeout 600 python bench.py --config $CFG --precision $PREC --steps 20 --warmup 5 --no-cpu-baseline --no-accurate --no-also --sustained-steps 0 --report $OUT/ab.json ${AB_EXTRA} > $OUT/ab.line 2> $OUT/ab.err || tail -5 $OUT/ab.err
+  env $envs RG_SKIP_PREFLIGHT=1 timeout 600 python bench.py --config $CFG --precision $PREC --steps 20 --warmup 5 --full --no-cpu-baseline --no-accurate --no-also --sustained-steps 0 --report $OUT/ab.json ${AB_EXTRA} > $OUT/ab.line 2> $OUT/ab.err || tail -5 $OUT/ab.err
   python - "$CFG $PREC $envs" <<'PY'
 import json, sys
 r = json.load(open("/root/repo/gpurun_out/ab.json"))

@@ -16,8 +16,8 @@ TAG=${1:-r01}
 } > $OUT/env_$TAG.log 2>&1
 echo "== smoke ==" ; timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG.log 2>&1; echo "smoke rc=$?" | tee -a $OUT/smoke_$TAG.log; tail -3 $OUT/smoke_$TAG.log
 echo "== pytest -m gpu =="; timeout 1200 python -m pytest tests -m gpu -q -x --no-header -p no:cacheprovider > $OUT/pytest_gpu_$TAG.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest_gpu_$TAG.log; tail -15 $OUT/pytest_gpu_$TAG.log
-echo "== bench bf16 =="; timeout 900 python bench.py --steps 30 --warmup 5 > $OUT/bench_bf16_$TAG.json 2> $OUT/bench_bf16_$TAG.err; echo "rc=$?"; cat $OUT/bench_bf16_$TAG.json; tail -5 $OUT/bench_bf16_$TAG.err
-echo "== bench f32 =="; timeout 900 python bench.py --steps 5 --warmup 2 --precision f32 --no-cpu-baseline > $OUT/bench_f32_$TAG.json 2> $OUT/bench_f32_$TAG.err; echo "rc=$?"; cat $OUT/bench_f32_$TAG.json; tail -5 $OUT/bench_f32_$TAG.err
+echo "== bench bf16 =="; timeout 900 python bench.py --steps 30 --warmup 5 --full > $OUT/bench_bf16_$TAG.json 2> $OUT/bench_bf16_$TAG.err; echo "rc=$?"; cat $OUT/bench_bf16_$TAG.json; tail -5 $OUT/bench_bf16_$TAG.err
+echo "== bench f32 =="; timeout 900 python bench.py --steps 5 --warmup 2 --precision f32 --full --no-cpu-baseline > $OUT/bench_f32_$TAG.json 2> $OUT/bench_f32_$TAG.err; echo "rc=$?"; cat $OUT/bench_f32_$TAG.json; tail -5 $OUT/bench_f32_$TAG.err
 echo "== rocprofv3 kernel trace =="
 cd /tmp && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o bench -- python /root/repo/bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-kernel-profile > $OUT/rocprof_$TAG.log 2>&1; echo "rocprof rc=$?"
 cd /root/repo

@@ -9,7 +9,7 @@ timeout 1500 python -m pytest tests -m gpu -q -s --no-header -p no:cacheprovider
 for spec in "c2 bf16" "c2 bf16x3" "c2 f32" "c3 bf16" "c4 bf16" "c4 bf16x3"; do
   set -- $spec
   extra=""; [ "$1 $2" != "c2 bf16" ] && extra="--no-cpu-baseline"
-  timeout 900 python bench.py --config $1 --precision $2 --steps 20 --warmup 5 $extra > $OUT/bench_$1_$2_$TAG.json 2> $OUT/bench_$1_$2_$TAG.err; echo "bench $1 $2 rc=$?"
+  timeout 900 python bench.py --config $1 --precision $2 --steps 20 --warmup 5 --full $extra > $OUT/bench_$1_$2_$TAG.json 2> $OUT/bench_$1_$2_$TAG.err; echo "bench $1 $2 rc=$?"
   python - <<PY
 import json
 try:

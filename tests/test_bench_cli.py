@@ -7,6 +7,7 @@ import subprocess
 import sys
 import types
 
+import numpy as np
 import pytest
 
 from conftest import free_port
@@ -106,7 +107,7 @@ def _measure_worker(rank, world, port, out_dir):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     argv = sys.argv
     sys.argv = ["bench.py", "--config", "c2", "--gpus", str(world), "--capacity", "1024", "--batch", "128", "--parity-batch", "128",
-                "--hidden", "256", "--layers", "2", "--precision", "bf16", "--steps", "2", "--warmup", "1", "--repeats", "2", "--sustained-steps", "3"]
+                "--hidden", "256", "--layers", "2", "--precision", "bf16", "--steps", "2", "--warmup", "1", "--repeats", "2", "--sustained-steps", "3", "--full"]
     try:
         args = bench.parse()
     finally:
@@ -292,7 +293,7 @@ def test_two_ranks_under_torchrun_print_one_compact_line(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
            "--master-port", str(free_port()), os.path.join(ROOT, "tests", "bench_on_emu.py"), "--gpus", "2", "--config", "c2",
            "--capacity", "1024", "--batch", "128", "--parity-batch", "128", "--hidden", "128", "--layers", "2", "--steps", "2",
-           "--warmup", "1", "--repeats", "2", "--sustained-steps", "2", "--report", str(report)]
+           "--warmup", "1", "--repeats", "2", "--sustained-steps", "2", "--report", str(report), "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -309,3 +310,42 @@ def test_two_ranks_under_torchrun_print_one_compact_line(tmp_path):
     full = json.load(open(report))
     assert [p["rank"] for p in full["per_rank"]] == [0, 1] and full["all_reduce_bytes"] > 0
     assert "eager" in full["config"]["launch"]
+
+
+def test_plain_run_times_the_steps_and_dumps_reproducible_outputs(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` without --full (tests/bench_on_emu.py): the line holds the
+    contract's keys and none of --full's objects, it names no report file, and the last step's outputs land in DIR as
+    float32 .npy files — the same bits on a second run with the same arguments"""
+    env = dict(os.environ, OMP_NUM_THREADS="2")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_on_emu.py"), "--gpus", "1", "--capacity", "1024", "--batch", "128",
+               "--hidden", "128", "--layers", "2", "--steps", "3", "--warmup", "1", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert all(k in line for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"))
+        assert line["steps"] == 3 and line["report"] is None and "roofline" not in line and "cpu_baseline" not in line
+        assert line["value"] == pytest.approx(128 / (line["ms_per_step"] * 1e-3), rel=1e-6)
+        dumps.append({f.name: np.load(f) for f in sorted(d.iterdir())})
+    a, b = dumps
+    assert "loss.npy" in a and "q_values.npy" in a and any(k.startswith("state.q_network_target.") for k in a)
+    assert a["q_values.npy"].shape == (128, 16) and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert set(a) == set(b) and all(x.dtype == np.float32 and np.array_equal(x, b[k]) for k, x in a.items())
+
+
+def test_dump_outputs_samples_the_largest_arrays_to_fit(tmp_path):
+    sys.path.insert(0, ROOT)
+    import bench
+
+    big, small = torch.arange(10000, dtype=torch.float64), torch.ones(3, 4, dtype=torch.bfloat16)
+    names = bench.dump_outputs(str(tmp_path), {"big/one": big, "small": small}, limit=4 * 2012)
+    assert names == ["big_one", "small"]
+    a, s = np.load(tmp_path / "big_one.npy"), np.load(tmp_path / "small.npy")
+    assert s.dtype == np.float32 and s.shape == (3, 4) and a.dtype == np.float32 and a.size == 2000
+    assert np.all(np.diff(a) > 0) and np.array_equal(a, np.load(tmp_path / "big_one.npy"))  # positions in ascending order
+    bench.dump_outputs(str(tmp_path / "again"), {"big/one": big, "small": small}, limit=4 * 2012)
+    assert np.array_equal(a, np.load(tmp_path / "again" / "big_one.npy"))  # a fixed sample

@@ -180,8 +180,15 @@ def test_head_lane_layouts_against_torch(backend, A, B, double_q, loss):
 
 
 def test_masked_softmax_matches_the_reference_function_bit_for_bit():
-    """core/torch_utils.masked_softmax is a restatement; where the reference tree is present (build container) it must give
-    the reference function's bits, everywhere it must be a softmax over the kept entries with zero rows for empty masks."""
+    """core/torch_utils.masked_softmax is a restatement: it must give the reference function's bits (its outputs recorded in
+    tests/golden/reference_records/masked_softmax_ref.npz, checked against the function itself where the reference tree is present) and be a
+    softmax over the kept entries with zero rows for empty masks."""
+    import os
+
+    import numpy as np
+
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_records", "masked_softmax_ref.npz")
+    rec = dict(np.load(golden)) if os.path.exists(golden) else {}
     g = torch.Generator().manual_seed(5)
     x = torch.randn(64, 7, generator=g) * 4
     mask = (torch.rand(64, 7, generator=g) < 0.6).float()
@@ -200,4 +207,12 @@ def test_masked_softmax_matches_the_reference_function_bit_for_bit():
             stubs.install()
             from reagent.core.torch_utils import masked_softmax as ref_fn
 
-            assert torch.equal(got, ref_fn(x, mask, temp))
+            want = ref_fn(x, mask, temp)
+            assert torch.equal(got, want)
+            if os.environ.get("RG_WRITE_GOLDEN") == "1":
+                rec[f"temp_{temp}"] = want.numpy().copy()
+            else:
+                assert torch.equal(torch.from_numpy(rec[f"temp_{temp}"]), want)
+        assert torch.equal(got, torch.from_numpy(rec[f"temp_{temp}"]))
+    if stubs.reference_available() and os.environ.get("RG_WRITE_GOLDEN") == "1":
+        np.savez_compressed(golden, **rec)

@@ -1,14 +1,15 @@
 """the Python surface is the reference's — constructor parameter NAMES, ORDER and DEFAULT VALUES of every
 class on the path equal the reference's own (`inspect.signature`), so a config / call site written for ReAgent binds
-the same way here.  Runs where the reference tree is present (the build container), in a subprocess so that
-`reagent` is importable through oracle/stubs.py.  Allowed additions: keyword parameters this package adds AFTER the
+the same way here.  The reference's side is recorded in tests/golden/reference_records/reference_signatures.json (read where the reference
+tree is present, in a subprocess so that `reagent` is importable through oracle/stubs.py).  Allowed additions: keyword parameters this package adds AFTER the
 reference's (listed in EXTRA below, e.g. `device=` of the replay buffers)."""
+import json
 import os
 import subprocess
 import sys
 import textwrap
 
-import pytest
+from oracle import stubs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -60,65 +61,94 @@ METHODS = [
 ]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/reagent"), reason="needs the reference tree (build container)")
-def test_constructor_and_method_signatures_equal_the_reference():
-    code = textwrap.dedent("""
-        import dataclasses, importlib, inspect, sys
-        sys.path.insert(0, %r)
-        from oracle import stubs
-        stubs.install()
-        stubs.install_gym()                   # the input makers live under reagent.gym (its envs need the uninstalled gym)
-        PAIRS, METHODS = %r, %r
+GOLDEN = os.path.join(ROOT, "tests", "golden", "reference_records", "reference_signatures.json")
 
-        def resolve(path):
-            mod, name = path.rsplit(".", 1)
-            return getattr(importlib.import_module(mod), name)
+# what a signature is reduced to (name, kind, default), the same on both sides
+_PARAMS = textwrap.dedent("""
+    import dataclasses, importlib, inspect
 
-        def default_of(p):
-            d = p.default
-            if isinstance(d, dataclasses.Field):            # resolve_defaults' field(default_factory=...): compare the factory
-                f = d.default_factory
-                return ("factory", getattr(f, "__qualname__", repr(f)).split(".")[-1])
-            if d is inspect.Parameter.empty:
-                return ("required",)
-            if repr(d) == "<factory>":                      # the __init__ a @dataclass generates for field(default_factory=...)
-                return ("factory", "dataclass")
-            if dataclasses.is_dataclass(d) or callable(d):
-                return ("object", type(d).__name__ if not callable(d) else getattr(d, "__name__", repr(d)))
-            return ("value", repr(d))
+    def resolve(path):
+        mod, name = path.rsplit(".", 1)
+        return getattr(importlib.import_module(mod), name)
 
-        def params(fn):
-            return [(n, p.kind.name, default_of(p)) for n, p in inspect.signature(fn).parameters.items() if n != "self"]
+    def default_of(p):
+        d = p.default
+        if isinstance(d, dataclasses.Field):            # resolve_defaults' field(default_factory=...): compare the factory
+            f = d.default_factory
+            return ["factory", getattr(f, "__qualname__", repr(f)).split(".")[-1]]
+        if d is inspect.Parameter.empty:
+            return ["required"]
+        if repr(d) == "<factory>":                      # the __init__ a @dataclass generates for field(default_factory=...)
+            return ["factory", "dataclass"]
+        if dataclasses.is_dataclass(d) or callable(d):
+            return ["object", type(d).__name__ if not callable(d) else getattr(d, "__name__", repr(d))]
+        return ["value", repr(d)]
 
-        def same(ref, own):
-            # the reference writes mutable defaults as field(default_factory=F) under @resolve_defaults
-            # (reagent/core/configuration.py); here such a parameter defaults to None and the constructor calls the same F
-            if len(ref) != len(own):
-                return False
-            for (rn, rk, rd), (on, ok, od) in zip(ref, own):
-                if (rn, rk) != (on, ok):
-                    return False
-                # (SACTrainer.alpha_optimizer: None means "fixed temperature" in both, so the stand-in for the factory there
-                # is the sentinel "default")
-                if rd != od and not (rd[0] == "factory" and od in (("value", "None"), ("value", "'default'"))):
-                    return False
-            return True
+    def params(fn):
+        return [[n, p.kind.name, default_of(p)] for n, p in inspect.signature(fn).parameters.items() if n != "self"]
 
-        bad = []
-        for ref_path, own_path, extra in PAIRS:
-            ref, own = params(resolve(ref_path).__init__), params(resolve(own_path).__init__)
-            tail = own[len(ref):]
-            if not same(ref, own[:len(ref)]) or [t[0] for t in tail] != list(extra) or any(t[2] == ("required",) for t in tail):
-                bad.append((own_path, "reference: %%r" %% (ref,), "here: %%r" %% (own,)))
-        for ref_path, own_path, names in METHODS:
-            for m in names:
-                ref, own = params(getattr(resolve(ref_path), m)), params(getattr(resolve(own_path), m))
-                if [(n, k) for n, k, _ in own[:len(ref)]] != [(n, k) for n, k, _ in ref] or any(t[2] == ("required",) for t in own[len(ref):]):
-                    bad.append((own_path + "." + m, "reference: %%r" %% (ref,), "here: %%r" %% (own,)))
-        for b in bad:
-            print("MISMATCH", *b, sep="\\n   ")
-        print("ok" if not bad else "failed")
-    """) % (ROOT, PAIRS, METHODS)
-    env = {k: v for k, v in os.environ.items() if k != "REAGENT_AMD_OWN_TYPES"}
+    def surface(paths_methods):
+        return {path: {m: params(getattr(resolve(path), m)) for m in methods} for path, methods in paths_methods}
+""")
+
+
+def _wanted(ref):
+    """(class path, the methods recorded for it) of one side: `__init__` of every pair plus the METHODS"""
+    out = {}
+    for r, o, _ in PAIRS:
+        out.setdefault(r if ref else o, ["__init__"])
+    for r, o, names in METHODS:
+        out.setdefault(r if ref else o, ["__init__"]).extend(n for n in names if n not in out[r if ref else o])
+    return sorted(out.items())
+
+
+def _surface(ref):
+    """{class path: {method: [[name, kind, default], ...]}} of the reference (through oracle/stubs.py) or of this package,
+    in a fresh interpreter so that `reagent` is importable only where it is asked for"""
+    pre = "import sys; sys.path.insert(0, %r)\n" % ROOT
+    if ref:
+        pre += "from oracle import stubs\nstubs.install()\nstubs.install_gym()\n"  # the input makers live under reagent.gym
+    code = pre + _PARAMS + "import json\nprint(json.dumps(surface(%r)))\n" % (_wanted(ref),)
+    env = {k: v for k, v in os.environ.items() if k != "REAGENT_AMD_OWN_TYPES"} if ref else dict(os.environ)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-6000:] + out.stderr[-3000:]
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
+    return json.loads(out.stdout.strip().splitlines()[-1])
+
+
+def _same(ref, own):
+    # the reference writes mutable defaults as field(default_factory=F) under @resolve_defaults
+    # (reagent/core/configuration.py); here such a parameter defaults to None and the constructor calls the same F
+    if len(ref) != len(own):
+        return False
+    for (rn, rk, rd), (on, ok, od) in zip(ref, own):
+        if (rn, rk) != (on, ok):
+            return False
+        # (SACTrainer.alpha_optimizer: None means "fixed temperature" in both, so the stand-in for the factory there
+        # is the sentinel "default")
+        if rd != od and not (rd[0] == "factory" and od in (["value", "None"], ["value", "'default'"])):
+            return False
+    return True
+
+
+def test_constructor_and_method_signatures_equal_the_reference():
+    """against the reference's signatures as recorded in tests/golden/reference_records/reference_signatures.json; where the reference tree
+    is present the record is checked against it first (RG_WRITE_GOLDEN=1 rewrites it from there)"""
+    if os.path.isdir(os.path.join(stubs.REFERENCE_ROOT, "reagent")):
+        live = _surface(ref=True)
+        if os.environ.get("RG_WRITE_GOLDEN") == "1":
+            with open(GOLDEN, "w") as f:
+                json.dump(live, f, indent=1, sort_keys=True)
+        assert live == json.load(open(GOLDEN)), "tests/golden/reference_records/reference_signatures.json is not what the reference has"
+    recorded, here = json.load(open(GOLDEN)), _surface(ref=False)
+    bad = []
+    for ref_path, own_path, extra in PAIRS:
+        ref, own = recorded[ref_path]["__init__"], here[own_path]["__init__"]
+        tail = own[len(ref):]
+        if not _same(ref, own[:len(ref)]) or [t[0] for t in tail] != list(extra) or any(t[2] == ["required"] for t in tail):
+            bad.append((own_path, "reference: %r" % (ref,), "here: %r" % (own,)))
+    for ref_path, own_path, names in METHODS:
+        for m in names:
+            ref, own = recorded[ref_path][m], here[own_path][m]
+            if [(n, k) for n, k, _ in own[:len(ref)]] != [(n, k) for n, k, _ in ref] or any(t[2] == ["required"] for t in own[len(ref):]):
+                bad.append((own_path + "." + m, "reference: %r" % (ref,), "here: %r" % (own,)))
+    assert not bad, "\n".join("MISMATCH " + "\n   ".join(b) for b in bad)

@@ -1,25 +1,52 @@
 """Drop-in detail of SURVEY §8 a8: inside a ReAgent installation the trainers must be annotated with the
 reference's OWN batch classes, because `make_trainer_preprocessor` looks the input maker up by class object
-(reagent/gym/preprocessors/trainer_preprocessor.py:39-48).  Runs where the reference tree is present (the build
-container), in a subprocess so that `reagent` is importable BEFORE reagent_amd is imported."""
+(reagent/gym/preprocessors/trainer_preprocessor.py:39-48).  Runs in a subprocess so that `reagent` is importable BEFORE
+reagent_amd is imported: the reference tree through oracle/stubs.py where it is present, elsewhere a stand-in `reagent`
+package whose `reagent.core.types` holds classes of its own (this package's restatements, loaded as a separate module)."""
 import os
 import subprocess
 import sys
 import textwrap
 
-import pytest
+from oracle import stubs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/reagent"), reason="needs the reference tree (build container)")
-def test_reference_batch_classes_are_used_when_reagent_is_importable():
+STAND_IN = textwrap.dedent("""
+    # stand-in for the reference's reagent.core.types: this package's restatements executed as a module of their own, so
+    # that its classes are distinct objects from the ones reagent_amd defines
+    import importlib.util, os
+    _keep = os.environ.get("REAGENT_AMD_OWN_TYPES")
+    os.environ["REAGENT_AMD_OWN_TYPES"] = "1"
+    try:
+        _spec = importlib.util.spec_from_file_location("reagent.core._restated", %r)
+        _m = importlib.util.module_from_spec(_spec)
+        _spec.loader.exec_module(_m)
+    finally:
+        os.environ.pop("REAGENT_AMD_OWN_TYPES")
+        if _keep is not None:
+            os.environ["REAGENT_AMD_OWN_TYPES"] = _keep
+    globals().update({k: v for k, v in vars(_m).items() if not k.startswith("__")})
+""") % os.path.join(ROOT, "reagent_amd", "core", "types.py")
+
+
+def test_reference_batch_classes_are_used_when_reagent_is_importable(tmp_path):
+    if os.path.isdir(os.path.join(stubs.REFERENCE_ROOT, "reagent")):
+        setup = "from oracle import stubs\nstubs.install()\n"  # the reference on sys.path with fakes for uninstalled deps
+    else:
+        core = tmp_path / "reagent" / "core"
+        core.mkdir(parents=True)
+        (tmp_path / "reagent" / "__init__.py").write_text("")
+        (core / "__init__.py").write_text("")
+        (core / "types.py").write_text(STAND_IN)
+        setup = "sys.path.insert(0, %r)\n" % str(tmp_path)
     code = textwrap.dedent("""
         import inspect, sys
         sys.path.insert(0, %r); sys.path.insert(0, %r)
-        from oracle import stubs
-        stubs.install()                       # puts /root/reference on sys.path with fakes for uninstalled deps
+    """) % (ROOT, os.path.join(ROOT, "tests")) + setup + textwrap.dedent("""
         import reagent.core.types as ref
+        assert ref.DiscreteDqnInput.__module__ != "reagent_amd.core.types"
         import reagent_amd.core.types as rlt
         assert rlt.USING_REFERENCE_TYPES and rlt.DiscreteDqnInput is ref.DiscreteDqnInput
         assert rlt.PolicyNetworkInput is ref.PolicyNetworkInput and rlt.FeatureData is ref.FeatureData
@@ -47,7 +74,7 @@ def test_reference_batch_classes_are_used_when_reagent_is_importable():
         loss = tr.train_step_native(batch)
         assert torch.isfinite(loss).all()
         print("ok")
-    """) % (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "tests"))
+    """) % (os.path.join(ROOT, "tests"),)
     env = {k: v for k, v in os.environ.items() if k != "REAGENT_AMD_OWN_TYPES"}
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stdout[-1500:] + out.stderr[-3000:]

@@ -2,6 +2,8 @@
 ReplayBuffer (tests/golden/replay_*.npz), (b) the reference's own known-answer tests
 (reagent/test/replay_memory/circular_replay_buffer_test.py:60-352, restated here), (c) the numpy
 oracle on a larger seeded case, and size-independent properties (gather == index_select)."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -267,14 +269,37 @@ def test_load_checkpoint_written_by_the_reference_layout_only(backend, tmp_path)
     assert fresh.size == rb.size
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/reagent"), reason="needs the reference checkout")
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _reference_tree():
+    from oracle import stubs
+
+    return os.path.isdir(os.path.join(stubs.REFERENCE_ROOT, "reagent"))
+
+
+def _write_golden():
+    return os.environ.get("RG_WRITE_GOLDEN") == "1"
+
+
+def _checkpoint_element(path):
+    """one file of a checkpoint as the reference's load reads it: gzip'd np.save, anything else pickled"""
+    import gzip
+    import io
+    import pickle
+
+    with gzip.open(path, "rb") as f:
+        raw = f.read()
+    try:
+        return np.load(io.BytesIO(raw), allow_pickle=False)
+    except ValueError:
+        return pickle.loads(raw)
+
+
 def test_checkpoints_interchange_with_the_reference_class(emu_lib, tmp_path):
-    """files written by the reference ReplayBuffer load here and vice versa (build container only)"""
-    from oracle import reference_harness as rh
-
-    rh._install()
-    from reagent.replay_memory.circular_replay_buffer import ReplayBuffer as RefBuffer
-
+    """files written by the reference ReplayBuffer load here and vice versa.  The reference's checkpoint of this fill (its
+    files byte for byte, and its validity mask) is recorded in tests/golden/reference_records/replay_checkpoint_ref.npz; where the reference
+    tree is present the record is checked against a fresh one and the reference class loads this package's files itself"""
     def fill(rb, n):
         rng = np.random.RandomState(4)
         for i in range(n):
@@ -283,21 +308,55 @@ def test_checkpoints_interchange_with_the_reference_class(emu_lib, tmp_path):
         return rb
 
     kw = dict(stack_size=1, replay_capacity=50, batch_size=8, update_horizon=2, gamma=0.9)
-    ref, mine = fill(RefBuffer(**kw), 37), fill(ReplayBuffer(device="cpu", **kw), 37)
+    golden = f"{GOLDEN_DIR}/reference_records/replay_checkpoint_ref.npz"
     d_ref, d_mine = tmp_path / "ref", tmp_path / "mine"
     d_ref.mkdir(), d_mine.mkdir()
-    ref.save(str(d_ref), 3)
+    mine = fill(ReplayBuffer(device="cpu", **kw), 37)
     mine.save(str(d_mine), 3)
+    ref = None
+    if _reference_tree():
+        from oracle import reference_harness as rh
+
+        rh._install()
+        from reagent.replay_memory.circular_replay_buffer import ReplayBuffer as RefBuffer
+
+        ref = fill(RefBuffer(**kw), 37)
+        d_live = tmp_path / "live"
+        d_live.mkdir()
+        ref.save(str(d_live), 3)
+        if _write_golden():
+            np.savez_compressed(golden, __is_index_valid=ref._is_index_valid.numpy(),
+                                **{f.name: np.frombuffer(f.read_bytes(), np.uint8) for f in d_live.iterdir()})
+    rec = np.load(golden)
+    for name in rec.files:
+        if name != "__is_index_valid":
+            (d_ref / name).write_bytes(rec[name].tobytes())
+    ref_valid = rec["__is_index_valid"]
+    if ref is not None:  # the record is what the reference writes today (gzip headers aside: compared decoded)
+        assert sorted(f.name for f in d_live.iterdir()) == sorted(f.name for f in d_ref.iterdir())
+        for f in d_live.iterdir():
+            a, b = _checkpoint_element(f), _checkpoint_element(d_ref / f.name)
+            assert (np.array_equal(a[:37], b[:37]) if f.name.startswith("$store$_") else np.array_equal(a, b)), f.name
+        assert np.array_equal(ref._is_index_valid.numpy(), ref_valid)
     assert {f.name for f in d_ref.iterdir()} <= {f.name for f in d_mine.iterdir()}  # same names (+ $rg$_ extras)
     loaded = fill(ReplayBuffer(device="cpu", **kw), 2)
     loaded.load(str(d_ref), 3)  # reference -> here
     assert int(loaded.add_count) == 37
-    np.testing.assert_array_equal(loaded._valid_host, ref._is_index_valid.numpy())
-    ref2 = fill(RefBuffer(**kw), 2)
-    ref2.load(str(d_mine), 3)  # here -> reference
-    assert int(ref2.add_count) == 37
-    for k in ref._store:  # rows never written are uninitialised memory in the reference
-        np.testing.assert_array_equal(ref2._store[k].numpy()[:37], ref._store[k].numpy()[:37])
+    np.testing.assert_array_equal(loaded._valid_host, ref_valid)
+    # here -> reference: every file the reference reads holds what the reference's own file holds (storage rows never
+    # written are uninitialised memory in the reference)
+    for f in d_ref.iterdir():
+        a, b = _checkpoint_element(f), _checkpoint_element(d_mine / f.name)
+        if f.name.startswith("$store$_"):
+            np.testing.assert_array_equal(b[:37], a[:37])
+        else:
+            assert np.array_equal(a, b), f.name
+    if ref is not None:
+        ref2 = fill(RefBuffer(**kw), 2)
+        ref2.load(str(d_mine), 3)
+        assert int(ref2.add_count) == 37
+        for k in ref._store:
+            np.testing.assert_array_equal(ref2._store[k].numpy()[:37], ref._store[k].numpy()[:37])
 
 
 def _fill_for_timeline(rb, n, discrete):
@@ -330,27 +389,55 @@ def test_pre_timeline_df_columns(emu_lib, discrete):
         assert set(row["action"]) == {0, 1} and "possible_actions" not in df.columns
 
 
-@pytest.mark.skipif(not __import__("os").path.isdir("/root/reference/reagent"), reason="needs the reference checkout")
+def _plain(x):
+    """a DataFrame cell as JSON-safe data that keeps what == tells apart (dict key types, nesting)"""
+    if isinstance(x, dict):
+        return {"__dict__": [[_plain(k), _plain(v)] for k, v in x.items()]}
+    if isinstance(x, (list, tuple)):
+        return [_plain(v) for v in x]
+    if isinstance(x, np.generic):
+        return x.item()
+    return x
+
+
 @pytest.mark.parametrize("discrete", [True, False])
 def test_pre_timeline_df_equals_the_reference(emu_lib, discrete):
-    """same buffer contents + same sampled indices -> the same DataFrame as the reference function"""
-    from oracle import reference_harness as rh
+    """same buffer contents + same sampled indices -> the same DataFrame as the reference function (its DataFrame and the
+    indices it drew recorded in tests/golden/reference_records/pre_timeline_df.json; where the reference tree is present the record is checked
+    against the reference function first)"""
+    import json
 
-    rh._install()
-    from reagent.replay_memory.circular_replay_buffer import ReplayBuffer as RefBuffer
-    from reagent.replay_memory.utils import replay_buffer_to_pre_timeline_df as ref_fn
     from reagent_amd.replay_memory.utils import replay_buffer_to_pre_timeline_df
 
+    golden = f"{GOLDEN_DIR}/reference_records/pre_timeline_df.json"
     kw = dict(stack_size=1, replay_capacity=40, batch_size=4)
-    ref = _fill_for_timeline(RefBuffer(**kw), 30, discrete)
+    if _reference_tree():
+        from oracle import reference_harness as rh
+
+        rh._install()
+        from reagent.replay_memory.circular_replay_buffer import ReplayBuffer as RefBuffer
+        from reagent.replay_memory.utils import replay_buffer_to_pre_timeline_df as ref_fn
+
+        ref = _fill_for_timeline(RefBuffer(**kw), 30, discrete)
+        rec = json.load(open(golden)) if os.path.exists(golden) else {}
+        # the reference draws the indices itself (unseeded): a new record draws them, a check reuses the recorded ones
+        idx = ref.sample_index_batch(ref.size) if _write_golden() else torch.tensor(rec[str(discrete)]["idx"], dtype=torch.int64)
+        ref.sample_index_batch = lambda n: idx
+        a = ref_fn(discrete, ref)
+        live = {"idx": idx.tolist(), "columns": list(a.columns), "values": {c: _plain(a[c].tolist()) for c in a.columns}}
+        if _write_golden():
+            rec[str(discrete)] = live
+            with open(golden, "w") as f:
+                json.dump(rec, f, sort_keys=True)
+        assert json.loads(json.dumps(live)) == rec[str(discrete)], "tests/golden/reference_records/pre_timeline_df.json is not what the reference gives"
+    rec = json.load(open(golden))[str(discrete)]
+    idx = torch.tensor(rec["idx"], dtype=torch.int64)
     mine = _fill_for_timeline(ReplayBuffer(device="cpu", **kw), 30, discrete)
-    idx = ref.sample_index_batch(ref.size)
-    ref.sample_index_batch = lambda n: idx
     mine.sample_index_batch = lambda n: idx.clone()
-    a, b = ref_fn(discrete, ref), replay_buffer_to_pre_timeline_df(discrete, mine)
-    assert list(a.columns) == list(b.columns) and len(a) == len(b)
-    for c in a.columns:
-        assert a[c].tolist() == b[c].tolist(), c
+    b = replay_buffer_to_pre_timeline_df(discrete, mine)
+    assert rec["columns"] == list(b.columns) and all(len(v) == len(b) for v in rec["values"].values())
+    for c in b.columns:
+        assert rec["values"][c] == json.loads(json.dumps(_plain(b[c].tolist()))), c
 
 
 def _gym_buffer(device, horizon, with_mask, n=90, cap=96, F=8, A=3, seed=12):
@@ -646,8 +733,10 @@ def test_reference_known_answers_replay_overflow(backend):
 @pytest.mark.parametrize("horizon", [1, 3])
 def test_add_many_equals_the_same_transitions_added_one_by_one(backend, horizon):
     """ReplayBuffer.add_many (bulk rows as one indexed device copy per column, the validity rules of add in closed form)
-    against `add` called per transition — and, in the build container, against the REFERENCE class's add: same storage,
-    cursor, validity mask, episode counter, over several calls, episode boundaries at every offset and two wraps of the ring."""
+    against `add` called per transition — and against the REFERENCE class's add (its validity mask and valid count after
+    every call recorded in tests/golden/reference_records/replay_add_many_ref.npz, checked against the class itself where the reference tree
+    is present): same storage, cursor, validity mask, episode counter, over several calls, episode boundaries at every
+    offset and two wraps of the ring."""
     import numpy as np
 
     from reagent_amd.replay_memory import ReplayBuffer
@@ -659,13 +748,15 @@ def test_add_many_equals_the_same_transitions_added_one_by_one(backend, horizon)
     ref = None
     from oracle import stubs
 
+    golden = f"{GOLDEN_DIR}/reference_records/replay_add_many_ref.npz"
+    rec = dict(np.load(golden)) if os.path.exists(golden) else {}
     if stubs.reference_available():
         stubs.install()
         from reagent.replay_memory.circular_replay_buffer import ReplayBuffer as RefBuffer
 
         ref = RefBuffer(replay_capacity=C, batch_size=4, update_horizon=horizon, gamma=0.9)
     total = 0
-    for T in (1, 2, 40, 7, 60, 97, 13, 1, 30):
+    for i, T in enumerate((1, 2, 40, 7, 60, 97, 13, 1, 30)):
         cols = dict(observation=rng.standard_normal((T, F)).astype(np.float32), action=rng.integers(0, A, T),
                     reward=rng.random(T).astype(np.float32), terminal=rng.random(T) < 0.15,
                     possible_actions_mask=(rng.random((T, A)) < 0.8).astype(np.float32), log_prob=rng.random(T).astype(np.float32))
@@ -685,9 +776,19 @@ def test_add_many_equals_the_same_transitions_added_one_by_one(backend, horizon)
         assert bulk._num_transitions_in_current_episode == one._num_transitions_in_current_episode
         for k in one._store:
             assert torch.equal(bulk._store[k].cpu(), one._store[k].cpu()), k
+        key = f"h{horizon}_{i}"
         if ref is not None:
             assert np.array_equal(bulk._valid_host, ref._is_index_valid.numpy()), (T, total)
             assert bulk._num_valid_indices == ref._num_valid_indices
+            if _write_golden():
+                rec[f"{key}_valid"], rec[f"{key}_n"] = ref._is_index_valid.numpy().copy(), np.int64(ref._num_valid_indices)
+            else:
+                assert np.array_equal(rec[f"{key}_valid"], ref._is_index_valid.numpy()) and rec[f"{key}_n"] == ref._num_valid_indices
+        # the reference's add as recorded in tests/golden/reference_records/replay_add_many_ref.npz
+        assert np.array_equal(bulk._valid_host, rec[f"{key}_valid"]), (T, total)
+        assert bulk._num_valid_indices == int(rec[f"{key}_n"])
+    if ref is not None and _write_golden():
+        np.savez_compressed(golden, **rec)
     # and the sampler reads the same batch from both
     idx = bulk._valid_indices()[:8]
     a, b = bulk.sample_transition_batch(8, indices=idx), one.sample_transition_batch(8, indices=idx)
