@@ -2,7 +2,7 @@
 // RG_STAMP hooks as s_memtime stamps.  C3 shapes: B = 65536 rows of 128 bf16 state features through a random row map, 3 x 512
 // trunk, 16 groups x 200 outputs (group g = rows [4096 g, 4096 g + 4096) of the grouped space: no boundary tiles), fp32 output
 // rows scattered back through the map (argv[1] = 1) or written in grouped order (0).
-// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../reagent_amd/csrc -I../../include [-DRG_GROUPED_WHOLE=0] grouped_phases.hip -o grouped_phases
+// Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -I../../reagent_amd/csrc -I../../include grouped_phases.hip -o grouped_phases
 #include <hip/hip_runtime.h>
 __device__ unsigned long long* g_stamps;
 #define RG_STAMP(slot)                                                                                   \
@@ -68,7 +68,7 @@ int main(int argc, char** argv) {
   for (int r = 0; r < 20; ++r) kern<<<n_wg, FB_NW * 64, lds>>>(a);
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
-  printf("grouped forward WHOLE=%d RING=%d scatter=%d: %.2f us/launch (stamps on), err=%d\n", RG_GROUPED_WHOLE, RG_GROUPED_RING, scatter, ms * 1e3 / 20,
+  printf("grouped forward RING=%d scatter=%d: %.2f us/launch (stamps on), err=%d\n", GROUPED_RING, scatter, ms * 1e3 / 20,
          (int)hipGetLastError());
   std::vector<unsigned long long> h((size_t)n_wg * NWV * NPH);
   hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);

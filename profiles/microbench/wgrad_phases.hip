@@ -66,9 +66,8 @@ int main() {
   unsigned long long tmin = ~0ull, tmax = 0;
   for (int g = 0; g < max_wg; ++g) for (int w = 0; w < 8; ++w) { const unsigned long long* s = &h[((size_t)g * 8 + w) * 8]; if (!s[6]) continue; if (s[5] < tmin) tmin = s[5]; if (s[6] > tmax) tmax = s[6]; }
   const double span = (double)(tmax - tmin);
-  printf("kernel span (first start -> last end): %.0f ticks; plan: RG_WGRAD_PLAN=%s RG_WGRAD_TOTAL=%s RG_WGRAD_UNSHARED=%s\n", span,
-         getenv("RG_WGRAD_PLAN") ? getenv("RG_WGRAD_PLAN") : "-", getenv("RG_WGRAD_TOTAL") ? getenv("RG_WGRAD_TOTAL") : "-",
-         getenv("RG_WGRAD_UNSHARED") ? getenv("RG_WGRAD_UNSHARED") : "-");
+  printf("kernel span (first start -> last end): %.0f ticks; plan: RG_WGRAD_TOTAL=%s\n", span,
+         getenv("RG_WGRAD_TOTAL") ? getenv("RG_WGRAD_TOTAL") : "-");
   for (int layer = 0; layer < 4; ++layer) {
     const unsigned long long key = ((unsigned long long)dims[layer + 1] << 32) | (unsigned)dims[layer];
     double tot[5] = {0}, life = 0, start = 0, end = 0, last = 0, first_end = 1e30;

@@ -73,7 +73,7 @@ int main(int argc, char** argv) {
   for (int r = 0; r < 20; ++r) kern<<<n_wg, FB_NW * 64, lds>>>(a);
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
-  printf("x3 forward NW=%d RING=%d save=%d: %.2f us/launch (stamps on), err=%d\n", FB_NW, RG_X3_RING, save, ms * 1e3 / 20, (int)hipGetLastError());
+  printf("x3 forward NW=%d RING=%d save=%d: %.2f us/launch (stamps on), err=%d\n", FB_NW, X3_RING, save, ms * 1e3 / 20, (int)hipGetLastError());
   std::vector<unsigned long long> h((size_t)n_wg * NWV * NPH);
   hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost);
   const char* names[NPH] = {"", "x tile load+barrier", "L0 mainloop(K=128)", "L0 pack", "L0 barrier wait", "L0 LDS store+barrier",

@@ -22,66 +22,22 @@
 #include "rg_mlp_frag.h"
 #include "rg_reduce.h"
 #include <cstdio>
-// workgroups per layer of the grouped weight-gradient launch (splits = this / tiles).
-// Round 3, same-box A/B in the C2 step (wgrad + reduce, us): this uniform 128 per layer 132-134; workgroups shared out in
-// proportion to the operand bytes a layer's tiles stream — 256 in all (one round on the chip, 52 MB of partials
-// instead of 84) 143-144, 384 in all 157, 512 in all 165; the tiles that share an operand half walking their split's
-// blocks 2 / 4 / 8 blocks apart (so that the second reader finds the line in L2 instead of joining the in-flight miss)
-// 143-145 / 162-164 / 172-173: the lockstep second reader is the cheap one.  Not kept.
-#ifndef RG_OUT_LDS
-#define RG_OUT_LDS 1  // a thin output layer's weight fragments resident in LDS (tile_kloop_ldsb)
-#endif
-#ifndef RG_BWD_SIGNS_EARLY
-#define RG_BWD_SIGNS_EARLY 1  // backward: the first step's sign planes are requested before the dout tile (0 = before its main loop)
-#endif
-#ifndef RG_GROUPED_STAGE_OUT
-#define RG_GROUPED_STAGE_OUT 1  // a wide grouped output leaves through the (dead) activation tile as whole rows
-#endif
-#ifndef RG_GROUPED_RING
-#define RG_GROUPED_RING 8   // weight chunks in flight per wave in that path's K loop
-#endif
-#ifndef RG_WGRAD_TARGET
-#define RG_WGRAD_TARGET 128
-#endif
-#ifndef RG_FWD_SWAP
-#define RG_FWD_SWAP 0  // non-saving forwards on transposed accumulator tiles (mlp_fwd_swap_kernel).  Round 4, same box: the two
-// non-saving forwards of a C2 step 169 -> 177 us, C4's 100 -> 106 — the 8-byte LDS writes collide two ways on the tile's row
-// pitch and the 16 bias values per tile are re-requested per row tile; bit-identical, slower: not the default.
-#endif
-#ifndef RG_WGRAD_BF16_PART
-#define RG_WGRAD_BF16_PART 1  // bf16 stack launch: split partials as bf16 tiles in accumulator order (WgradFragArgs.part_mode)
-#endif
-#ifndef RG_WGRAD_PART_NT
-#define RG_WGRAD_PART_NT 0   // bf16 partial tiles: bit 0 = non-temporal stores (wgrad), bit 1 = non-temporal loads (reduce).  Round 5,
-#endif                       // same box: 0 / 1 / 2 / 3 all within 1 us of each other; plain stores and loads are the default
-#ifndef RG_WGRAD_UNEVEN
-#define RG_WGRAD_UNEVEN 125  // stack launch: uneven splits of the multi-tile layers (rg_mlp_wgrad_fused); value = cost of a single-tile
-#endif                       // workgroup's block in percent of a multi-tile one's; 0 = every split of a layer the same length
-#ifndef RG_REDUCE_FLY
-#define RG_REDUCE_FLY 16      // split-reduce: fp32 partials requested per thread before the first add (multiple of 4; 4 = rounds 1-4)
-#endif
-#ifndef RG_REDUCE_FLY_BF16
-#define RG_REDUCE_FLY_BF16 8  // the same for the 32-byte bf16 tile records (even)
-#endif
-#ifndef RG_WGRAD_PIPE
-#define RG_WGRAD_PIPE 1  // weight gradient: LDS fragment reads one half ahead of the MFMAs (wgrad_shape_core)
-#endif
-#ifndef RG_WGRAD_PAIR
-#define RG_WGRAD_PAIR 0  // weight gradient, 256 x 256 tiles: two 32-row blocks per barrier (measured +5 %: not the default)
-#endif
 
 namespace rg {
+
+// workgroups per layer of the stack's weight-gradient launch (splits = this / tiles); the alternatives measured against it
+// are in profiles/NOTES_r01_r05.md
+constexpr int WGRAD_TARGET = 128;
+constexpr int GROUPED_RING = 8;      // weight chunks in flight per wave in the grouped whole-tile output's K loop
+constexpr int REDUCE_FLY = 16;       // split-reduce: fp32 partials requested per thread before the first add (multiple of 4)
+constexpr int REDUCE_FLY_BF16 = 8;   // the same for the 32-byte bf16 tile records (even)
 
 // NW waves per workgroup, each owning 32*TN columns of a hidden layer (hidden width = 32*TN*NW).
 // NW = 4 (one wave per SIMD, up to 512 registers each): 16 accumulator tiles per wave and a weight
 // ring deep enough to cover the L2 latency from a single wave.  NW = 8: two waves per SIMD.
 template <int NW> struct MlpCfg {
   static constexpr int THREADS = NW * 64;
-#ifdef RG_FUSED_RING
-  static constexpr int RING = RG_FUSED_RING;
-#else
   static constexpr int RING = NW == 4 ? 8 : 2;
-#endif
 };
 
 // Grouped forward, the LAST segment of a tile (mlp_fwd_fused_body): wave w sums column tile w of the group's [N, K] layer for all four
@@ -104,7 +60,7 @@ __device__ __forceinline__ void grouped_whole_tile_out(bf16_t* act, int pitch, i
   float b = 0.f;
   if (wave < NTo) {
     if (b_out && col < N) b = b_out[col];  // (requested before the K loop)
-    wide_mainloop<1, RG_GROUPED_RING>(act, pitch, KC, wf_out + (long)wave * KC * 512, 0, acc4, lane, k_rotation(blockIdx.x, wave, KC));
+    wide_mainloop<1, GROUPED_RING>(act, pitch, KC, wf_out + (long)wave * KC * 512, 0, acc4, lane, k_rotation(blockIdx.x, wave, KC));
   }
   RG_STAMP(16);
   __syncthreads();  // every wave is done reading the layer input
@@ -140,9 +96,7 @@ __device__ __forceinline__ void grouped_whole_tile_out(bf16_t* act, int pitch, i
 // tile assignment loses the dispatcher's load balancing; the kernel stays one tile per workgroup.)
 // GROUPED: the launch of a stack whose output layer takes per-tile weights (rg_mlp_desc.tile_key, qr_grouped.hip) is its
 // own instantiation — the ordinary kernel does not carry its code paths (or their registers).
-// SWAP (round 4): the non-saving launch of the plain kernel computes its hidden layers with transposed accumulator tiles
-// (rg_mlp_frag.h: wide_mainloop<.., SWAP>, fwd_hidden_pack_swapped) — same values bit for bit, a cheaper epilogue.
-template <int TN, int NW, int PITCH, bool GROUPED, bool SWAP = false>
+template <int TN, int NW, int PITCH, bool GROUPED>
 __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
   constexpr int THREADS = MlpCfg<NW>::THREADS, RING = MlpCfg<NW>::RING;
   RG_DYN_LDS(smem);
@@ -194,22 +148,17 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[tm][tn][r] = 0.f;
       const long nt_stride = (long)KC * 512;
-      wide_mainloop<TN, RING, SWAP>(act, pitch, KC, a.wfrag[l] + (long)(wave * TN) * nt_stride, nt_stride, acc, lane,
-                                    k_rotation(blockIdx.x, wave, KC), wave / (NW / 2));
+      wide_mainloop<TN, RING>(act, pitch, KC, a.wfrag[l] + (long)(wave * TN) * nt_stride, nt_stride, acc, lane,
+                              k_rotation(blockIdx.x, wave, KC), wave / (NW / 2));
       RG_STAMP(2 + 4 * l);
       unsigned PK[4][TN][8];
-      if constexpr (SWAP) {
-        RG_DISPATCH_ACT(a.acts[l], (fwd_hidden_pack_swapped<TN, A_>(acc, a.bias[l], wave, lane, PK)));
-      } else {
-        unsigned* sign_dst = a.save ? a.act_sign[l + 1] : nullptr;  // plane base; the lane offset is applied at the store
-        RG_DISPATCH_ACT(a.acts[l], (fwd_hidden_pack<TN, A_>(acc, a.bias[l], fwd_save_dst(a, l),
-                                                            sign_dst, N / 32, tile * 4, wave, lane, PK)));
-      }
+      unsigned* sign_dst = a.save ? a.act_sign[l + 1] : nullptr;  // plane base; the lane offset is applied at the store
+      RG_DISPATCH_ACT(a.acts[l], (fwd_hidden_pack<TN, A_>(acc, a.bias[l], fwd_save_dst(a, l),
+                                                          sign_dst, N / 32, tile * 4, wave, lane, PK)));
       RG_STAMP(3 + 4 * l);
       __syncthreads();  // every wave is done reading the layer input
       RG_STAMP(4 + 4 * l);
-      if constexpr (SWAP) store_packed_tiles_swapped<TN>(act, pitch, PK, wave, lane);
-      else store_packed_tiles<TN>(act, pitch, PK, wave, lane);
+      store_packed_tiles<TN>(act, pitch, PK, wave, lane);
       if (out_lds) RG_WAIT_VMCNT(0);  // this wave's share of the output layer's weights has landed (long ago) ...
       __syncthreads();                // ... and after the barrier every wave's has
       RG_STAMP(5 + 4 * l);
@@ -272,9 +221,9 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
           RG_STAMP(16);
           __syncthreads();  // every wave is done reading the layer input
           RG_STAMP(17);
-          // RG_OUT_ROWSTORE (round 5): the 128 x N outputs leave as whole rows, 16 bytes per lane, through the (dead) activation
-          // tile — 8 wave stores of 1 KB for 16 Q-values instead of 64 four-byte ones from the accumulators that each touch
-          // 32 half-lines (fwd_phases: "sum + stores" 4.6k of a workgroup's 83k ticks -> 3.1k, the launch 84.6 -> 79.2 us).
+          // The 128 x N outputs leave as whole rows, 16 bytes per lane, through the (dead) activation tile — 8 wave stores of
+          // 1 KB for 16 Q-values instead of 64 four-byte ones from the accumulators that each touch 32 half-lines (round 5's
+          // A/B: profiles/NOTES_r01_r05.md).
           // Both halves of K put their partial sums into the staging area ([half][row][N] floats) and the row-store pass adds
           // them — (lower + upper) + bias, the order of the accumulator hand-off below — one barrier instead of two.
           // (everything the row store needs is worked out HERE, from an opaque copy of the lane: hoisted above the hidden layers'
@@ -284,7 +233,7 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
           // and a full tile — the tile's 128 x N block as ONE contiguous run, whatever N is
           const bool aligned16 = (reinterpret_cast<uintptr_t>(a.out32) & 15) == 0;
           const bool dense_run = a.ldo == N && row_base + FB_BM <= a.batch;
-          const bool rowstore = RG_OUT_ROWSTORE && !a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0));
+          const bool rowstore = !a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0));
           if (rowstore) {  // (workgroup-uniform)
             float* outs = (float*)act + half * (FB_BM * 32);
             float* bias_s = (float*)act + 2 * (FB_BM * 32);  // the bias (requested before the K loop) travels through LDS too
@@ -341,7 +290,7 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
               store_tile(acc, tm, 0);
             }
           }
-        } else if (GROUPED && RG_GROUPED_STAGE_OUT && NTo <= NW && a.stage_out) {
+        } else if (GROUPED && NTo <= NW && a.stage_out) {
           // Grouped output layer, wide (QR-DQN: 200 quantiles per row).  Stored straight from the accumulators a wave
           // instruction writes two 128-byte row segments that start 32 * row bytes off a cache line (rows are 800 bytes):
           // partial lines, 54 MB of them per launch (-20..-28 us with the stores removed).  Here the output leaves as
@@ -349,8 +298,7 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
           // area BEHIND the activation tile (32 x (32 NTo + 4) floats, 29 KB of the 30 KB the tile leaves of the CU's LDS).
           const int P = NTo * 32 + 4;  // floats per staged row
           const int np = N >> 2;       // 16-byte pieces per row
-#if RG_GROUPED_WHOLE
-          // Round 6.  The per-row-tile loop below is a chain of L2 round trips: each of its four passes runs tile_kloop (4 weight
+          // The per-row-tile loop below is a chain of L2 round trips: each of its four passes runs tile_kloop (4 weight
           // chunks in flight per wave, 8 dependent groups) and two barriers — ~45k of the workgroup's cycles for 8k of MFMAs.
           // The LAST segment of a tile (the only one of a tile inside one group's range: all but <= n_groups - 1 tiles of a
           // launch) leaves the activation tile dead after its K loop, so there: wave w sums column tile w for ALL FOUR row tiles
@@ -367,7 +315,6 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
                                        a.batch, a.out32, a.ldo);
             break;  // (the last segment)
           }
-#endif
           float* stage = (float*)(act + FB_BM * pitch);
           for (int tm = tm0; tm < tm1; ++tm) {
             if (wave < NTo) {
@@ -415,12 +362,6 @@ template <int TN, int NW, int PITCH>
 __global__ void RG_LAUNCH_BOUNDS(NW * 64, 1) mlp_fwd_grouped_kernel(MlpArgs a) {
   mlp_fwd_fused_body<TN, NW, PITCH, true>(a);
 }
-#if RG_FWD_SWAP
-template <int TN, int NW, int PITCH>
-__global__ void RG_LAUNCH_BOUNDS(NW * 64, 1) mlp_fwd_swap_kernel(MlpArgs a) {  // save == 0 only
-  mlp_fwd_fused_body<TN, NW, PITCH, false, true>(a);
-}
-#endif
 
 // DX_ONLY: a frozen stack — only the input gradient is produced, no dZ fragments are written (rg_mlp_desc.dx_only)
 // GROUPED: the stack's output layer takes per-group weights (rg_mlp_desc.tile_key / row_begin): its own instantiation, the
@@ -461,10 +402,10 @@ __device__ __forceinline__ void mlp_bwd_fused_body(const MlpArgs& a) {
     }
   };
   unsigned sg_first[2 * TN];
-  if (RG_BWD_SIGNS_EARLY && L >= 2) request_signs(L - 1, sg_first);
+  if (L >= 2) request_signs(L - 1, sg_first);
   // ... and when that step's K is ONE chunk (<= 16 outputs: Q-values, a critic's scalar) so do its weight fragments: the step is
   // then four LDS reads and 4 x TN MFMAs instead of an L2 round trip behind the tile's barrier (bwd_phases: 2.7k cycles).
-  const bool first_one_chunk = RG_BWD_SIGNS_EARLY && !GROUPED && L >= 2 && a.dims[L] <= 16;
+  const bool first_one_chunk = !GROUPED && L >= 2 && a.dims[L] <= 16;
   u16x8 w_first[TN];
   if (first_one_chunk) {
     const bf16_t* wl = a.wfrag[L - 1] + (long)(wave * TN) * 512 + lane * 8;  // KC = 1: one 512-element record per n-tile
@@ -499,7 +440,7 @@ __device__ __forceinline__ void mlp_bwd_fused_body(const MlpArgs& a) {
     // sign bits of H_l, requested before the main loop so they are in registers at the epilogue
     unsigned sg[2 * TN];
     const bool use_sign = a.act_sign[l] != nullptr;
-    if (RG_BWD_SIGNS_EARLY && l == L - 1) {
+    if (l == L - 1) {
 #pragma unroll
       for (int i = 0; i < 2 * TN; ++i) sg[i] = sg_first[i];
     } else {
@@ -636,7 +577,6 @@ struct WgradFragArgs {
   // contiguous (32 bytes) — so a tile leaves as two 16-byte stores per lane instead of sixteen 4-byte ones and the launch
   // writes (and its reduce reads) half the bytes; slab = NTa * NTb * 512 floats' worth.  The reduce launch undoes the order.
   int part_mode;
-  int part_nt;        // part_mode 1: bit 0 = the partial tiles leave as non-temporal stores (RG_WGRAD_PART_NT, A/B switch)
 };
 
 
@@ -733,10 +673,8 @@ __device__ __forceinline__ void wgrad_shape_core(const WgradFragArgs& g, int ng,
   const bool wave_has_tiles = wn * TA < na && wk * TB < nb;  // a wave whose tiles are all padding skips its MFMAs
   // Round 4 (profiles/microbench/out/r04a/wgrad_phases.txt): an iteration of this loop took ~2700 cycles whatever the stage
   // held — 16 MFMAs per wave (1024 cycles per SIMD), the rest LDS latency, DMA issue and the barrier: the loop is bound
-  // by its own per-iteration chain, not by the memory system (8 % of it waits for data).  So (a) the fragments of the next
-  // 16-row half are requested from LDS before the MFMAs of the current one (RG_WGRAD_PIPE), and (b) the square shape,
-  // whose ring has four slots, takes TWO blocks per barrier (RG_WGRAD_PAIR): one wait, one barrier and one burst of DMA
-  // issues per 32 MFMAs of a wave instead of per 16, the next pair in flight meanwhile.
+  // by its own per-iteration chain, not by the memory system (8 % of it waits for data).  So the fragments of the next
+  // 16-row half are requested from LDS before the MFMAs of the current one.
   auto load_half = [&](int slot, int h, u16x8 (&af)[TA], u16x8 (&bf)[TB]) {
     const char* base = smem + slot * S::STAGE_BYTES + h * 1024 + lane * 16;
 #pragma unroll
@@ -750,74 +688,37 @@ __device__ __forceinline__ void wgrad_shape_core(const WgradFragArgs& g, int ng,
 #pragma unroll
       for (int j = 0; j < TB; ++j) acc[i][j] = mfma_32x32x16_bf16(af[i], bf[j], acc[i][j]);
   };
-  // the halves of `nb_` consecutive blocks whose first slot is slot0 (slots advance modulo the ring)
-  auto compute = [&](int slot0, auto nb_c) __attribute__((always_inline)) {
-    constexpr int NH = 2 * decltype(nb_c)::value;
+  // the two halves of the block in `slot`
+  auto compute = [&](int slot) __attribute__((always_inline)) {
     if (!wave_has_tiles) return;
-#if RG_WGRAD_PIPE
     u16x8 af[2][TA], bf[2][TB];
-    load_half(slot0, 0, af[0], bf[0]);
-    static_for<0, NH>([&](auto q_c) __attribute__((always_inline)) {
-      constexpr int q = decltype(q_c)::value;
-      if constexpr (q + 1 < NH) load_half((slot0 + (q + 1) / 2) % SLOTS, (q + 1) & 1, af[(q + 1) & 1], bf[(q + 1) & 1]);
+    load_half(slot, 0, af[0], bf[0]);
+    static_for<0, 2>([&](auto h_c) __attribute__((always_inline)) {
+      constexpr int h = decltype(h_c)::value;
+      if constexpr (h == 0) load_half(slot, 1, af[1], bf[1]);
       sched_fence();  // (without the fences the scheduler requests every half's fragments up front: 256 registers + scratch)
-      mma_half(af[q & 1], bf[q & 1]);
+      mma_half(af[h], bf[h]);
       sched_fence();
     });
-#else
-    static_for<0, NH>([&](auto q_c) __attribute__((always_inline)) {
-      constexpr int q = decltype(q_c)::value;
-      u16x8 af[TA], bf[TB];
-      load_half((slot0 + q / 2) % SLOTS, q & 1, af, bf);
-      mma_half(af, bf);
-    });
-#endif
   };
-  using one_t = std::integral_constant<int, 1>;
-  using two_t = std::integral_constant<int, 2>;
-  constexpr bool PAIR = RG_WGRAD_PAIR && SLOTS == 4;
 
   RG_PHASE_INIT();
   if (mb_begin < mb_end) {
     const int n_blk = mb_end - mb_begin;
-    if constexpr (PAIR) {
-      // pair p = blocks 2p, 2p + 1 in slots (2p) % 4, (2p + 1) % 4; while it is computed pair p + 1 travels into the other
-      // two slots, which every wave left before this iteration's barrier
-      const int n_pair = n_blk >> 1;
-      issue(mb_begin, 0);
-      issue(mb_begin + 1, 1);
-      RG_PHASE(0);
-      for (int p = 0; p < n_pair; ++p) {
-        wait_vmcnt<0>();
-        RG_PHASE(2);
-        raw_barrier();
-        RG_PHASE(3);
-        issue(mb_begin + 2 * p + 2, (2 * p + 2) & 3);
-        issue(mb_begin + 2 * p + 3, (2 * p + 3) & 3);
-        compute((2 * p) & 3, two_t{});
-        RG_PHASE(1);
-      }
-      wait_vmcnt<0>();
-      if (n_blk & 1) {  // an odd tail block (it travelled as the first block of the pair after the last; outside the
-        raw_barrier();  // loop: a second path through the accumulators INSIDE it doubled the kernel's registers)
-        compute((2 * n_pair) & 3, one_t{});
-      }
-    } else {
-      static_for<0, FLY>([&](auto f_c) __attribute__((always_inline)) { issue(mb_begin + decltype(f_c)::value, decltype(f_c)::value); });
-      RG_PHASE(0);
-      for (int t = 0; t < n_blk; ++t) {
-        // FLY stages are outstanding: let the oldest land, then meet the other waves — past the barrier block t is complete
-        // in LDS and every wave has finished reading block t-1, whose slot the DMA issued below overwrites
-        wait_vmcnt<(FLY - 1) * DMA>();
-        RG_PHASE(2);
-        raw_barrier();
-        RG_PHASE(3);
-        issue(mb_begin + t + FLY, (t + FLY) % SLOTS);  // before the MFMAs: the requests leave a block time earlier
-        compute(t % SLOTS, one_t{});
-        RG_PHASE(1);
-      }
-      wait_vmcnt<0>();
+    static_for<0, FLY>([&](auto f_c) __attribute__((always_inline)) { issue(mb_begin + decltype(f_c)::value, decltype(f_c)::value); });
+    RG_PHASE(0);
+    for (int t = 0; t < n_blk; ++t) {
+      // FLY stages are outstanding: let the oldest land, then meet the other waves — past the barrier block t is complete
+      // in LDS and every wave has finished reading block t-1, whose slot the DMA issued below overwrites
+      wait_vmcnt<(FLY - 1) * DMA>();
+      RG_PHASE(2);
+      raw_barrier();
+      RG_PHASE(3);
+      issue(mb_begin + t + FLY, (t + FLY) % SLOTS);  // before the MFMAs: the requests leave a block time earlier
+      compute(t % SLOTS);
+      RG_PHASE(1);
     }
+    wait_vmcnt<0>();
   }
 
   if (g.part_mode == 1) {
@@ -833,8 +734,8 @@ __device__ __forceinline__ void wgrad_shape_core(const WgradFragArgs& g, int ng,
           const f32x16& c = acc[i][j];
           const pk4_t v0 = pk4_t{pack_bf16x2(c[0], c[1]), pack_bf16x2(c[2], c[3]), pack_bf16x2(c[4], c[5]), pack_bf16x2(c[6], c[7])};
           const pk4_t v1 = pk4_t{pack_bf16x2(c[8], c[9]), pack_bf16x2(c[10], c[11]), pack_bf16x2(c[12], c[13]), pack_bf16x2(c[14], c[15])};
-          if (g.part_nt & 1) { stream_store(v0, dst); stream_store(v1, dst + 1); }
-          else { dst[0] = v0; dst[1] = v1; }
+          dst[0] = v0;
+          dst[1] = v1;
         }
       }
     RG_PHASE(4);
@@ -1108,18 +1009,15 @@ struct ReduceGroupArgs {
   float* out[FB_MAXL];
   // part_mode 1 layers (WgradFragArgs.part_mode): bf16 partial tiles in accumulator order; N x K = valid extents of dW
   int mode[FB_MAXL], NTb[FB_MAXL], N[FB_MAXL], K[FB_MAXL];
-  int nt_loads;  // part_mode 1: the partial tiles are read with non-temporal loads (RG_WGRAD_PART_NT bit 1)
 };
 
 // One 256-thread workgroup = one 32 x 32 tile: wave w sums the lane records (16 values, 32 contiguous bytes per split) of the
-// w-th quarter of the splits — all of a quarter's records requested before the first is added (RG_REDUCE_FLY_BF16 at a
+// w-th quarter of the splits — all of a quarter's records requested before the first is added (REDUCE_FLY_BF16 at a
 // time): the launch runs on loads in flight, 148 workgroups of one wave each were 16 dependent round trips — the four
 // quarter sums meet in LDS and are added in a fixed order.  Writes the row-major dW.
-template <bool NT>
 __device__ __forceinline__ void reduce_tiles_bf16(const float* part, long slab, int splits, float* out, int NTb, int N, int K,
                                                   long t, float (*red)[16][64]) {
   typedef __attribute__((ext_vector_type(4))) unsigned pk4_t;
-  auto stream_load = [](const pk4_t* p) { return NT ? rg::stream_load(p) : *p; };  // (the partials are read exactly once)
   const int lane = (int)(t & 63), w = (int)((t >> 6) & 3);
   const long tile = t >> 8;
   const int tn = (int)(tile / NTb), tk = (int)(tile % NTb);
@@ -1141,13 +1039,14 @@ __device__ __forceinline__ void reduce_tiles_bf16(const float* part, long slab, 
   const int per = (splits + 3) >> 2;
   int k = w * per;
   const int k_end = (k + per < splits) ? k + per : splits;
-  constexpr int U = RG_REDUCE_FLY_BF16;
+  constexpr int U = REDUCE_FLY_BF16;
   for (; k + U <= k_end; k += U) {
     pk4_t a[U], b[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      a[u] = stream_load((const pk4_t*)(p + (k + u) * stride));
-      b[u] = stream_load((const pk4_t*)(p + (k + u) * stride) + 1);
+      const pk4_t* rec = (const pk4_t*)(p + (k + u) * stride);
+      a[u] = rec[0];
+      b[u] = rec[1];
     }
 #pragma unroll
     for (int u = 0; u < U; u += 2) {
@@ -1156,12 +1055,15 @@ __device__ __forceinline__ void reduce_tiles_bf16(const float* part, long slab, 
     }
   }
   for (; k + 1 < k_end; k += 2) {
-    const pk4_t a0 = stream_load((const pk4_t*)(p + k * stride)), b0 = stream_load((const pk4_t*)(p + k * stride) + 1);
-    const pk4_t a1 = stream_load((const pk4_t*)(p + (k + 1) * stride)), b1 = stream_load((const pk4_t*)(p + (k + 1) * stride) + 1);
-    add(s0, a0, b0);
-    add(s1, a1, b1);
+    const pk4_t* r0 = (const pk4_t*)(p + k * stride);
+    const pk4_t* r1 = (const pk4_t*)(p + (k + 1) * stride);
+    add(s0, r0[0], r0[1]);
+    add(s1, r1[0], r1[1]);
   }
-  if (k < k_end) add(s0, stream_load((const pk4_t*)(p + k * stride)), stream_load((const pk4_t*)(p + k * stride) + 1));
+  if (k < k_end) {
+    const pk4_t* r0 = (const pk4_t*)(p + k * stride);
+    add(s0, r0[0], r0[1]);
+  }
 #pragma unroll
   for (int r = 0; r < 16; ++r) red[w][r][lane] = s0[r] + s1[r];
   __syncthreads();
@@ -1190,22 +1092,21 @@ __device__ __forceinline__ void reduce_group_body(const ReduceGroupArgs& R, long
     }
   if (mode == 1) {  // (whole workgroups: a layer's range is 256 threads per tile)
     __shared__ float red[4][16][64];
-    if (R.nt_loads) reduce_tiles_bf16<true>(part, slab, splits, out, NTb, N, K, i - base, red);
-    else reduce_tiles_bf16<false>(part, slab, splits, out, NTb, N, K, i - base, red);
+    reduce_tiles_bf16(part, slab, splits, out, NTb, N, K, i - base, red);
     return;
   }
   const long e = i - base;
   float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
   int k = 0;
 #define RG_LDP(p) stream_load(p)  // the split partials are read exactly once
-  // RG_REDUCE_FLY loads in flight per thread (round 5; see reduce_tiles_bf16): 32 splits were 8 dependent round trips per wave.
+  // REDUCE_FLY loads in flight per thread (round 5; see reduce_tiles_bf16): 32 splits were 8 dependent round trips per wave.
   // Same four chains, same order of additions: bit-identical to the 4-deep loop below.
-  for (; k + RG_REDUCE_FLY <= splits; k += RG_REDUCE_FLY) {
-    float v[RG_REDUCE_FLY];
+  for (; k + REDUCE_FLY <= splits; k += REDUCE_FLY) {
+    float v[REDUCE_FLY];
 #pragma unroll
-    for (int u = 0; u < RG_REDUCE_FLY; ++u) v[u] = RG_LDP(part + (long)(k + u) * slab + e);
+    for (int u = 0; u < REDUCE_FLY; ++u) v[u] = RG_LDP(part + (long)(k + u) * slab + e);
 #pragma unroll
-    for (int u = 0; u < RG_REDUCE_FLY; u += 4) {
+    for (int u = 0; u < REDUCE_FLY; u += 4) {
       s0 += v[u];
       s1 += v[u + 1];
       s2 += v[u + 2];
@@ -1690,7 +1591,7 @@ int rg_mlp_forward_fused(const rg_mlp_desc* d, const void* x, int x_dtype, int64
   {
     // a thin output layer (one column tile, the K-split path of the 8-wave kernel) reads its weights from LDS
     const int L = d->n_layers, KCo = (d->dims[L - 1] + 15) / 16;
-    if (RG_OUT_LDS && !d->tile_key && L >= 2 && d->dims[L] <= 16 && FB_NW == 8 && KCo >= 8 && (KCo & 1) == 0 &&
+    if (!d->tile_key && L >= 2 && d->dims[L] <= 16 && FB_NW == 8 && KCo >= 8 && (KCo & 1) == 0 &&
         lds + (size_t)KCo * 512 <= 160 * 1024) {
       a.out_lds = 1;
       lds += (size_t)KCo * 512;
@@ -1706,9 +1607,6 @@ int rg_mlp_forward_fused(const rg_mlp_desc* d, const void* x, int x_dtype, int64
     }
   }
   if (d->tile_key) RG_LAUNCH_FUSED(mlp_fwd_grouped_kernel, d->dims[1], a.pitch, grid, lds, stream, a);
-#if RG_FWD_SWAP
-  else if (save == 0) RG_LAUNCH_FUSED(mlp_fwd_swap_kernel, d->dims[1], a.pitch, grid, lds, stream, a);
-#endif
   else RG_LAUNCH_FUSED(mlp_fwd_fused_kernel, d->dims[1], a.pitch, grid, lds, stream, a);
   return (int)hipGetLastError();
 }
@@ -1803,21 +1701,14 @@ struct WgradFragPlan {
   long slab;
   int shape, tiles;  // workgroup tile shape (WG_SHAPE_*) and the number of such tiles that cover dW
 };
-// RG_WGRAD_SHAPES = 0: every layer on 256 x 256 tiles (rounds 1-3; same-box A/B switch)
-#ifndef RG_WGRAD_SHAPES
-#define RG_WGRAD_SHAPES 1
-#endif
 // workgroups per layer whose dW is ONE tile of its shape (dW0, thin output layers): their partial slab is the whole dW, so
 // the 128 of the multi-tile layers would double the partial bytes they had as two tiles x 64 splits
-#ifndef RG_WGRAD_TARGET_THIN
-#define RG_WGRAD_TARGET_THIN 64
-#endif
+constexpr int WGRAD_TARGET_THIN = 64;
 // the shape that stages the fewest bytes for an NTa x NTb-tile dW: groups x 16-byte units per thread and 32-row block
 static int wgrad_pick_shape(int NTa, int NTb, int x3, int* tiles_out) {
   static const int dma[WG_N_SHAPES] = {WgS8x8::DMA, WgS16x4::DMA, WgS4x16::DMA, WgS2x16::DMA, WgS1x16::DMA};
   int best = WG_SHAPE_8x8, best_cost = 0, best_tiles = 0;
   for (int sh = 0; sh < WG_N_SHAPES; ++sh) {
-    if (sh != WG_SHAPE_8x8 && !RG_WGRAD_SHAPES) continue;
     (void)x3;  // (the split-bf16 core takes the same shapes: its stage is the same bytes)
     const int ga = wgrad_shape_ga(sh), gb = wgrad_shape_gb(sh);
     const int tiles = ((NTa + ga - 1) / ga) * ((NTb + gb - 1) / gb);
@@ -1860,7 +1751,7 @@ int rg_fc_wgrad_frag(const void* dz_frag, const void* x_frag, int out_features, 
   g.a_frag = (const bf16_t*)dz_frag; g.b_frag = (const bf16_t*)x_frag;
   g.NTa = p.NTa; g.NTb = p.NTb; g.MB = p.MB; g.mb_base = 0; g.mb_per_split = p.mb_per_split; g.splits = p.splits;
   g.partial = (float*)workspace; g.slab = p.slab; g.N = out_features; g.K = in_features;
-  g.x3 = 0; g.a_lo = g.b_lo = 0; g.shape = p.shape; g.part_mode = 0; g.part_nt = 0;
+  g.x3 = 0; g.a_lo = g.b_lo = 0; g.shape = p.shape; g.part_mode = 0;
   const int grid = p.tiles * ((p.splits + 7) / 8 * 8);
   const size_t lds = (size_t)WG_SHAPED_LDS;
   RG_ALLOW_LDS(wgrad_frag_kernel, lds);
@@ -1896,7 +1787,7 @@ int rg_group_head_wgrad(const void* dz_frag, const void* h_frag, const int32_t* 
   G.g.x3 = x3 ? 1 : 0;
   G.g.a_lo = x3 ? (long)frag_elems(grouped_dz_rows(rows, n_groups), group_rows) : 0;
   G.g.b_lo = x3 ? (long)frag_elems(rows, in_features) : 0;
-  G.g.shape = WG_SHAPE_8x8; G.g.part_mode = 0; G.g.part_nt = 0;
+  G.g.shape = WG_SHAPE_8x8; G.g.part_mode = 0;
   G.row_begin = row_begin; G.n_groups = n_groups; G.splits = splits;
   const int k_groups = (G.g.NTb + 7) / 8;
   const size_t lds = (size_t)WgS8x8::LDS_BYTES;
@@ -1944,23 +1835,19 @@ int rg_mlp_stage_weights_fused(const rg_mlp_desc* d, int need_bwd, rg_stream_t s
 // in its L2; LDS fragment reads and MFMAs cost nothing on top, the partial tiles do: 67 MB of them, written when the
 // workgroups of a round finish together, are 20 us.  The launch of rounds 1-3 gave every layer 128 workgroups: 512 of
 // uneven length (a dW0 workgroup half as long as a hidden layer's) in dispatch order — the CU that drew dW0 then a hidden
-// layer finished last, at 3/2 of a balanced schedule — and 86 MB of partials.  Balanced plan: the splits of each layer are
-// chosen so that ALL workgroups of the launch are one round of the chip (RG_WGRAD_TOTAL, default = the CU count) and
-// take the same time by the rates above: fewer partial bytes, no tail.  (Round 3's "256 in all" experiment lost because a
-// split count that is not a multiple of 8 fell off the XCD-grouped decode: every byte then came from HBM twice.)
-struct WgradTuning { int balanced, total; double shared, unshared; int thin, long_first, bf16_part, uneven, part_nt; };
+// layer finished last, at 3/2 of a balanced schedule — and 86 MB of partials.  (A cost-model plan that makes all workgroups
+// one round of the chip was measured slower in round 4: profiles/NOTES_r01_r05.md.)
+// The plan's knobs, overridable from the environment so that tests can make a small stack meet the full-size plan:
+// total = the CU count (what the uneven split below assumes one round of the chip to be), thin = the workgroups of a
+// single-tile layer (WGRAD_TARGET_THIN), uneven = the single-tile block cost in percent of a multi-tile one's (125; 0 = every
+// split of a layer the same length).
+struct WgradTuning { int total, thin, uneven; };
 static const WgradTuning& wgrad_tuning() {
   static const WgradTuning t = [] {
-    WgradTuning v{0, 0, 46.0, 28.0, RG_WGRAD_TARGET_THIN, 1, RG_WGRAD_BF16_PART, RG_WGRAD_UNEVEN, RG_WGRAD_PART_NT};
-    if (const char* e = getenv("RG_WGRAD_PART_NT")) v.part_nt = atoi(e);
-    if (const char* e = getenv("RG_WGRAD_BF16_PART")) v.bf16_part = atoi(e);
+    WgradTuning v{0, WGRAD_TARGET_THIN, 125};
     if (const char* e = getenv("RG_WGRAD_UNEVEN")) v.uneven = atoi(e);
     if (const char* e = getenv("RG_WGRAD_THIN")) v.thin = atoi(e);
-    if (const char* e = getenv("RG_WGRAD_ORDER")) v.long_first = atoi(e);
-    if (const char* e = getenv("RG_WGRAD_PLAN")) v.balanced = (e[0] == 'b');  // "balanced": one round by the cost model
     if (const char* e = getenv("RG_WGRAD_TOTAL")) v.total = atoi(e);
-    if (const char* e = getenv("RG_WGRAD_SHARED")) v.shared = atof(e);
-    if (const char* e = getenv("RG_WGRAD_UNSHARED")) v.unshared = atof(e);
     if (v.total <= 0) {
       int dev = 0;
       hipDeviceProp_t pr;
@@ -1989,28 +1876,7 @@ static WgradFragPlan wgrad_group_plan(int out_f, int in_f, int batch, int target
 }
 
 static void wgrad_stack_plan(const rg_mlp_desc* d, int batch, WgradFragPlan* out) {
-  const WgradTuning& T = wgrad_tuning();
-  if (!T.balanced) {
-    for (int l = 0; l < d->n_layers; ++l) out[l] = wgrad_group_plan(d->dims[l + 1], d->dims[l], batch, RG_WGRAD_TARGET, d->x3);
-    return;
-  }
-  static const int dma[WG_N_SHAPES] = {WgS8x8::DMA, WgS16x4::DMA, WgS4x16::DMA, WgS2x16::DMA, WgS1x16::DMA};
-  double work[FB_MAXL], sum = 0.0;
-  for (int l = 0; l < d->n_layers; ++l) {
-    out[l] = wgrad_frag_plan(d->dims[l + 1], d->dims[l], batch, d->x3);
-    const double stage_bytes = dma[out[l].shape] * WG_THREADS * 16.0;
-    work[l] = (double)out[l].tiles * out[l].MB * stage_bytes / (out[l].tiles > 1 ? T.shared : T.unshared);
-    sum += work[l];
-  }
-  for (int l = 0; l < d->n_layers; ++l) {
-    WgradFragPlan& p = out[l];
-    int want = (int)(T.total * work[l] / sum / p.tiles + 0.5);
-    if (want > p.MB) want = p.MB;
-    if (want < 1) want = 1;
-    const int per = (p.MB + want - 1) / want;
-    p.mb_per_split = per;
-    p.splits = (p.MB + per - 1) / per;
-  }
+  for (int l = 0; l < d->n_layers; ++l) out[l] = wgrad_group_plan(d->dims[l + 1], d->dims[l], batch, WGRAD_TARGET, d->x3);
 }
 
 // floats a split's slab takes in the stack launch: N * K row-major, or NTa * NTb bf16 tile records of 2 KB (a thin layer's
@@ -2044,14 +1910,14 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
   long el = 0;
   // bf16 stacks: the splits' partial tiles as bf16 in accumulator order (half the bytes written here and read by the
   // reduce; error 2^-9 of a PARTIAL sum, far inside what bf16 operands cost the gradient).  Split-bf16 stacks: fp32.
-  const int part_mode = (!d->x3 && wgrad_tuning().bf16_part) ? 1 : 0;
+  const int part_mode = d->x3 ? 0 : 1;
   // ---- entries of the launch.  An entry is a layer, or one of the two CLASSES of splits of an unevenly split layer.
   // Round 4: the layers whose workgroups run longest go first (workgroups are dispatched in id order, one per CU: with dW0's
   // short ones first the launch ended at 3/2 of a balanced schedule).  Round 5: that order still leaves a staircase — at C2
   // 256 hidden-layer workgroups of 64 blocks take every CU, then the 128 single-tile ones (dW0, the output layer: 32 blocks)
   // run on half of the chip while the other half idles: 96 block times for 80 of work per CU.  The splits of the multi-tile
   // layers are therefore cut UNEVENLY: a fraction f = (single-tile workgroups) / (multi-tile workgroups) of each layer's
-  // splits is shorter by what a single-tile workgroup costs (b blocks, weighted by RG_WGRAD_UNEVEN percent: its stage is a
+  // splits is shorter by what a single-tile workgroup costs (b blocks, weighted by WgradTuning::uneven percent: its stage is a
   // single-reader stream, dearer per block), L1 = L - (1 - f) b, the others longer, L2 = L + f b.  Launch order L2 | L1 |
   // single-tile: the CUs that drew an L1 workgroup are the ones that free up for a single-tile one, and every CU ends at ~L2.
   struct Entry { int layer, mb_base, mb_end, per, splits, split_base; };
@@ -2071,7 +1937,7 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
       if (plan[l].tiles > 1) n_multi += plan[l].tiles * plan[l].splits;
       else { n_single += plan[l].splits; single_blocks += (double)plan[l].splits * plan[l].mb_per_split; }
     }
-    const bool uneven = T.uneven > 0 && !T.balanced && !(d->wgrad_flags & 1) && n_multi == T.total && n_single > 0 &&
+    const bool uneven = T.uneven > 0 && !(d->wgrad_flags & 1) && n_multi == T.total && n_single > 0 &&
                         n_single <= n_multi && d->n_layers + 2 <= WG_MAXV;
     const double f = uneven ? (double)n_single / n_multi : 0.0;
     const double b = uneven ? single_blocks / n_single * T.uneven / 100.0 : 0.0;
@@ -2094,9 +1960,8 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
       ent[n_ent++] = Entry{l, 0, cut, L2, s_long, 0};
       ent[n_ent++] = Entry{l, cut, p.MB, L1 > 0 ? L1 : 1, s_short, s_long};
     }
-    if (T.long_first)
-      for (int i = 1; i < n_ent; ++i)  // stable insertion sort by descending blocks per split
-        for (int j = i; j > 0 && ent[j].per > ent[j - 1].per; --j) { const Entry t = ent[j]; ent[j] = ent[j - 1]; ent[j - 1] = t; }
+    for (int i = 1; i < n_ent; ++i)  // stable insertion sort by descending blocks per split
+      for (int j = i; j > 0 && ent[j].per > ent[j - 1].per; --j) { const Entry t = ent[j]; ent[j] = ent[j - 1]; ent[j - 1] = t; }
   }
   if (getenv("RG_WGRAD_DEBUG")) {  // the launch plan, once per distinct shape (diagnostics: profiles/scripts)
     static int shown_batch = -1, shown_layers = -1;
@@ -2120,9 +1985,6 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
       part_of[l] = part; slab_of[l] = slab;
       R.partial[l] = part; R.slab[l] = slab; R.splits[l] = p.splits; R.out[l] = d->dw[l];
       R.mode[l] = part_mode; R.NTb[l] = p.NTb; R.N[l] = out_f; R.K[l] = in_f;
-#ifdef RG_WGRAD_LAYER_MASK  // timing ablation only (profiles/scripts): layers outside the mask get no workgroups, dW = 0
-      if (!((RG_WGRAD_LAYER_MASK >> l) & 1)) R.splits[l] = 0;
-#endif
       part += (size_t)p.splits * slab;
       el += part_mode == 1 ? (long)p.NTa * p.NTb * 256 : p.slab;  // threads of the reduce launch: a workgroup per tile, or one per element
     } else {
@@ -2132,7 +1994,6 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
     }
   }
   G.n = n_ent;
-  R.nt_loads = (wgrad_tuning().part_nt >> 1) & 1;
   for (int j = 0; j < WG_MAXV; ++j) {  // workgroup ranges in launch order
     G.wg_begin[j] = wg;
     if (j >= n_ent) {
@@ -2151,12 +2012,7 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
     g.a_lo = d->x3 ? (long)frag_elems(batch, d->dims[l + 1]) : 0;
     g.b_lo = d->x3 ? (long)frag_elems(batch, d->dims[l]) : 0;
     g.part_mode = part_mode;
-    g.part_nt = wgrad_tuning().part_nt;
-    int splits = e.splits;
-#ifdef RG_WGRAD_LAYER_MASK
-    if (!((RG_WGRAD_LAYER_MASK >> l) & 1)) splits = g.splits = 0;
-#endif
-    wg += p.tiles * ((splits + 7) / 8 * 8);  // the tiles of a split on ONE XCD (wgrad_frag_body), eight splits abreast
+    wg += p.tiles * ((e.splits + 7) / 8 * 8);  // the tiles of a split on ONE XCD (wgrad_frag_body), eight splits abreast
   }
   G.wg_begin[WG_MAXV] = wg;
   R.elem_begin[FB_MAXL] = el;

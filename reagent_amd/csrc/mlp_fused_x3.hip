@@ -22,14 +22,11 @@
 // autograd backward, in the accuracy class of the reference's fp32 CPU arithmetic.
 #include "rg_mlp_frag.h"
 
-// weight-fragment ring depth of the 8-wave kernels.  Round 3, same box, C2 step: ring 2 1.128-1.139 ms against 1.143-1.144
-// with ring 4 (saving forward 234 -> 227 us, backward 192 -> 188) — as for the bf16 kernels, a deeper ring only lengthens
-// the L2 queues.
-#ifndef RG_X3_RING
-#define RG_X3_RING 2
-#endif
-
 namespace rg {
+
+// weight-fragment ring depth of the 8-wave kernels: as for the bf16 kernels, a deeper ring only lengthens the L2 queues
+// (round 3's A/B: profiles/NOTES_r01_r05.md)
+constexpr int X3_RING = 2;
 
 constexpr int X3_TM = X3_BM / 32;
 
@@ -473,9 +470,7 @@ __device__ __forceinline__ void x3_bwd_pack(f32x16 (&acc)[X3_TM][TN], const bf16
 // Grouped forward, the LAST segment of a 64-row unit (mlp_fwd_x3_body; the bf16 kernel's grouped_whole_tile_out on two planes):
 // wave w sums column tile w of the group's [N, K] layer for both row tiles in the pipelined main loop, the 64 x N outputs are
 // staged in the activation planes — dead once every wave has left its K loop — and leave as whole rows, a wave per row.
-#ifndef RG_X3_GROUPED_RING
-#define RG_X3_GROUPED_RING 4
-#endif
+constexpr int X3_GROUPED_RING = 4;
 template <int NW, int LO>
 __device__ __forceinline__ void x3_grouped_whole_unit_out(bf16_t* act, int pitch, int KC, const bf16_t* wf_out, long wlo, const float* b_out,
                                                           int N, int NTo, int out_act, int lo, int hi, int row_base, const int* scatter,
@@ -491,7 +486,7 @@ __device__ __forceinline__ void x3_grouped_whole_unit_out(bf16_t* act, int pitch
   float b = 0.f;
   if (wave < NTo) {
     if (b_out && col < N) b = b_out[col];  // (requested before the K loop)
-    x3_mainloop<1, RG_X3_GROUPED_RING, LO>(act, pitch, KC, wf_out + (long)wave * KC * 512, wlo, 0, acc2, lane, k_rotation(blockIdx.x, wave, KC));
+    x3_mainloop<1, X3_GROUPED_RING, LO>(act, pitch, KC, wf_out + (long)wave * KC * 512, wlo, 0, acc2, lane, k_rotation(blockIdx.x, wave, KC));
   }
   __syncthreads();  // every wave is done reading the layer input
   float* stage = (float*)act;
@@ -521,7 +516,7 @@ __device__ __forceinline__ void x3_grouped_whole_unit_out(bf16_t* act, int pitch
 // bf16 kernel's tiles do (grouped_tile), and the launch is its own instantiation.
 template <int TN, int NW, int PITCH, bool GROUPED>
 __device__ __forceinline__ void mlp_fwd_x3_body(const MlpArgs& a) {
-  constexpr int THREADS = NW * 64, RING = RG_X3_RING, LO = X3_BM * PITCH;
+  constexpr int THREADS = NW * 64, RING = X3_RING, LO = X3_BM * PITCH;
   RG_DYN_LDS(smem);
   bf16_t* act = (bf16_t*)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
@@ -603,8 +598,7 @@ __device__ __forceinline__ void mlp_fwd_x3_body(const MlpArgs& a) {
           // write partial cache lines)
           const int P = NTo * 32 + 4;  // floats per staged row
           const int np = N >> 2;       // 16-byte pieces per row
-#if RG_GROUPED_WHOLE
-          // Round 6 (as mlp_fwd_fused_body): the LAST segment of a unit leaves both activation planes dead after its K loop —
+          // As in mlp_fwd_fused_body: the LAST segment of a unit leaves both activation planes dead after its K loop —
           // wave w sums column tile w for both row tiles in the pipelined main loop (one weight stream per wave instead of a
           // chain of x3_tile_kloop round trips per row tile), the 64 x N outputs are staged in the dead planes and leave as whole rows
           bool last_segment = false;
@@ -618,7 +612,6 @@ __device__ __forceinline__ void mlp_fwd_x3_body(const MlpArgs& a) {
                                               a.out_scatter ? a.rowmap : nullptr, a.batch, a.out32, a.ldo);
             break;
           }
-#endif
           float* stage = (float*)(act + 2 * LO);
           for (int tm = tm0; tm < tm1; ++tm) {
             if (wave < NTo) {
@@ -674,13 +667,13 @@ __device__ __forceinline__ void mlp_fwd_x3_body(const MlpArgs& a) {
       const int out_act = a.acts[l];
       constexpr int PARTS = NW / X3_TM;  // waves per tile when there is one column tile
       const bool split = NTo == 1 && KC >= 4 * PARTS;
-      // RG_OUT_ROWSTORE (round 5, as in mlp_fwd_fused_body): a thin output layer's [64, N] result leaves as whole 16-byte pieces
+      // As in mlp_fwd_fused_body: a thin output layer's [64, N] result leaves as whole 16-byte pieces
       // — rows (N % 4 == 0) or, for a dense output and a full tile, the tile's block as one run (a critic's single column) —
       // through a staging area in the dead activation planes: every part puts its partial sums there and the store pass adds
       // them, ((p0 + p1) + p2) + p3 + bias as the accumulator hand-off below does; the bias is requested BEFORE the K loop.
       const bool aligned16 = (reinterpret_cast<uintptr_t>(a.out32) & 15) == 0;
       const bool dense_run = a.ldo == N && row_base + X3_BM <= a.batch;
-      const bool rowstore = RG_OUT_ROWSTORE && split && !a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0));
+      const bool rowstore = split && !a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0));
       if (rowstore) {  // (workgroup-uniform; NW == PARTS * X3_TM waves, one (part, row tile) each)
         const int tm = wave % X3_TM, part = wave / X3_TM, per = (KC / PARTS + 1) / 2 * 2;
         const int lo = part * per, hi = part == PARTS - 1 ? KC : lo + per;
@@ -779,7 +772,7 @@ __global__ void RG_LAUNCH_BOUNDS(NW * 64, 1) mlp_fwd_x3_grouped_kernel(MlpArgs a
 // masked copies of both dZ planes
 template <int TN, int NW, int PITCH, bool DX_ONLY, bool GROUPED = false>
 __device__ __forceinline__ void mlp_bwd_x3_body(const MlpArgs& a) {
-  constexpr int THREADS = NW * 64, RING = RG_X3_RING, LO = X3_BM * PITCH;
+  constexpr int THREADS = NW * 64, RING = X3_RING, LO = X3_BM * PITCH;
   RG_DYN_LDS(smem);
   bf16_t* act = (bf16_t*)smem;
   const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);

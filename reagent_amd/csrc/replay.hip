@@ -49,9 +49,6 @@ struct GatherTable {
 // aligned unit (16 B when the row pitch allows, else the element size).  One workgroup moves
 // ROWS_PER_WG rows of one column; consecutive lanes take consecutive 16-B pieces of a row so a
 // 512-B observation row is one fully coalesced half-wave request.
-#ifndef RG_GATHER_REGCOLS
-#define RG_GATHER_REGCOLS 1  // replay_dqn_batch_kernel: column descriptors as a structure of arrays in LDS (16-byte, conflict-free reads)
-#endif
 constexpr int GATHER_ROWS_PER_WG = 64;
 constexpr int GATHER_MAX_LDS_COLS = 512;  // descriptors of one column staged in LDS (12 KB)
 
@@ -366,7 +363,6 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
   // 24-byte records at a lane stride of 96 bytes — an 8-way bank conflict each: PMC (profiles/r04_pmc) showed the LDS pipe
   // busy for half of the launch, 74 % of those cycles conflicts.  Same arithmetic, same bits.
   const int cpr = F >> 2;  // F % 4 == 0 (checked by the host)
-#if RG_GATHER_REGCOLS
   int* s_op = (int*)s_nc;                       // [GATHER_MAX_LDS_COLS] each, inside the same 12 KB
   float* s_p0 = (float*)s_nc + GATHER_MAX_LDS_COLS;
   float* s_p1 = s_p0 + GATHER_MAX_LDS_COLS;
@@ -384,7 +380,9 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
     const int total = nrows * cpr;
     for (int it = threadIdx.x; it < total; it += blockDim.x) {
       const int r = it / cpr, ch = it - r * cpr;
-      const f32x4 raw = stream_load((const f32x4*)(v.observation + s_src[r] * F + ch * 4));  // (read once: streaming, see below)
+      // a sampled row is read once: streaming load, so that 67 MB of replay rows per batch do not push the networks'
+      // weights out of L2 (same-box A/B with the streaming reduce loads: C2 step -2.8 %)
+      const f32x4 raw = stream_load((const f32x4*)(v.observation + s_src[r] * F + ch * 4));
       float w[4] = {raw[0], raw[1], raw[2], raw[3]};
       if (cols) {
         const i32x4 op = *(const i32x4*)(s_op + ch * 4);
@@ -399,36 +397,6 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
           }
           w[e] = normalize_value(c, w[e], 1.f, quantiles);
         }
-      }
-      const long at = (long)(row0 + r) * F + ch * 4;
-      if (o.state_dtype == RG_DT_BF16) {
-        uint2 pk;
-        pk.x = pack_bf16x2(w[0], w[1]);
-        pk.y = pack_bf16x2(w[2], w[3]);
-        *(uint2*)((bf16_t*)dst + at) = pk;
-      } else {
-        *(f32x4*)((float*)dst + at) = f32x4{w[0], w[1], w[2], w[3]};
-      }
-    }
-    return;
-  }
-#else
-  if (piece < 2 && cols)
-    for (int j = threadIdx.x; j < F; j += blockDim.x) s_nc[j] = cols[j];
-  __syncthreads();
-#endif
-  if (piece < 2) {
-    void* dst = piece == 0 ? o.state : o.next_state;
-    const int total = nrows * cpr;
-    for (int it = threadIdx.x; it < total; it += blockDim.x) {
-      const int r = it / cpr, ch = it - r * cpr;
-      // a sampled row is read once: streaming load, so that 67 MB of replay rows per batch do not push the networks'
-      // weights out of L2 (same-box A/B with the streaming reduce loads: C2 step -2.8 %)
-      const f32x4 raw = stream_load((const f32x4*)(v.observation + s_src[r] * F + ch * 4));
-      float w[4] = {raw[0], raw[1], raw[2], raw[3]};
-      if (cols) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) w[e] = normalize_value(s_nc[ch * 4 + e], w[e], 1.f, quantiles);
       }
       const long at = (long)(row0 + r) * F + ch * 4;
       if (o.state_dtype == RG_DT_BF16) {

@@ -25,22 +25,7 @@ namespace rg {
 
 constexpr int FB_BM = 128;
 constexpr int WG_THREADS = 512;  // weight-gradient kernels
-#ifndef RG_FUSED_WAVES
-#define RG_FUSED_WAVES 8
-#endif
-constexpr int FB_NW = RG_FUSED_WAVES;  // waves per workgroup of the forward / backward kernels (4 or 8)
-#ifndef RG_SIGN_STORE16
-#define RG_SIGN_STORE16 1  // saving forward, 512-wide stacks: a lane's sign words of both column tiles leave as one 16-byte store
-#endif
-#ifndef RG_OUT_ROWSTORE
-#define RG_OUT_ROWSTORE 1  // forwards: a thin output layer's [rows, N] result leaves as whole 16-byte pieces through LDS
-// (round 5, same box: fwd_phases 84.6 -> 79.2 us per launch, C2 step 0.495-0.508 -> 0.482 ms; a critic's single dense column as one
-// run per tile: C4 step 1.750 -> 1.708 ms.  Split-bf16 forward: a first form with an extra barrier lost 2 %; with every part's partial
-// sums staged — one barrier fewer — and the bias requested before the K loop: C2 step 1.136 -> 1.125 ms, C4 4.15 -> 4.115.)
-#endif
-#ifndef RG_SAVE_NT
-#define RG_SAVE_NT 1  // saved fragments leave as non-temporal stores (store_packed_frags; same-box A/B switch)
-#endif
+constexpr int FB_NW = 8;  // waves per workgroup of the forward / backward kernels
 constexpr int FB_MAXL = RG_MLP_MAX_LAYERS;
 
 // Split-bf16 stacks: how many bf16 planes of dZ the STACK'S weight gradient multiplies (RG_X3_DZ_PLANES, default below).
@@ -281,11 +266,7 @@ __device__ __forceinline__ void store_packed_frags(bf16_t* dst, int mb, int nt, 
     // streaming store: the fragments are read next by another launch (the weight gradient), never again by this one,
     // and should not push the weights out of L2 (same-box A/B: the consuming wgrad launch 137 -> 131 us)
     const u32x4 v = u32x4{P[4 * h], P[4 * h + 1], P[4 * h + 2], P[4 * h + 3]};
-#if RG_SAVE_NT
     stream_store(v, (u32x4*)(dst + frag_offset(mb, nt, NT, h, lane)));
-#else
-    *(u32x4*)(dst + frag_offset(mb, nt, NT, h, lane)) = v;
-#endif
   }
 }
 
@@ -308,19 +289,9 @@ __device__ __forceinline__ unsigned positive_bits(const float (&v)[16]) {
 // more than one XCD's 4 MB L2 when every XCD sees every group).  The hardware places block b on XCD b % 8, so XCD x takes
 // the x-th EIGHTH of the tile list: its L2 then serves the slices of ~G/8 groups.  The launch has 8 * ceil(n_tiles / 8)
 // blocks; those whose tile is past the end return at once.
-#ifndef RG_GROUPED_WHOLE
-#define RG_GROUPED_WHOLE 1  // grouped forward, a tile's last segment: pipelined K loop per column tile + whole-tile staging (round 6)
-#endif
-#ifndef RG_GROUPED_XCD
-#define RG_GROUPED_XCD 1
-#endif
 __device__ __forceinline__ int grouped_tile(int block, int n_tiles) {
-#if RG_GROUPED_XCD
   const int per = (n_tiles + 7) >> 3;
   return (block & 7) * per + (block >> 3);
-#else
-  return block;
-#endif
 }
 
 // Grouped row space (qr_grouped.hip): group g owns the rows [row_begin[g], row_begin[g + 1]) — padded per group to whole
@@ -388,10 +359,7 @@ __device__ __forceinline__ int k_rotation(int wg, int wave, int KC) { return (wg
 // accumulator on its way to the VALU, forward 78.9 -> 91.4 us (profiles/NOTES_r06.md §5, §9).
 __device__ __forceinline__ f32x16 mfma_main(u16x8 a, u16x8 b, f32x16 c) { return mfma_32x32x16_bf16(a, b, c); }
 
-// SWAP: the MFMA takes the WEIGHT fragment as its A operand and the activation fragment as B (the two fragment layouts are
-// the same registers: lane = row / column index, 8 consecutive k) — the accumulator tile is then the TRANSPOSE: lane =
-// batch row, register r = feature (r & 3) + 8 (r >> 2) + 4 (lane >> 5) of the tile.  Same products, same order over k.
-template <int TN, int RING, bool SWAP = false>
+template <int TN, int RING>
 __device__ __forceinline__ void wide_mainloop(const bf16_t* act, int pitch, int KC, const bf16_t* wf_wave,
                                               long nt_stride, f32x16 (&acc)[4][TN], int lane, int rot,
                                               int prio_phase = 0) {
@@ -415,7 +383,7 @@ __device__ __forceinline__ void wide_mainloop(const bf16_t* act, int pitch, int 
 #pragma unroll
     for (int tm = 0; tm < 4; ++tm)
 #pragma unroll
-      for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = SWAP ? mfma_main(bf[tn], af[tm], acc[tm][tn]) : mfma_main(af[tm], bf[tn], acc[tm][tn]);
+      for (int tn = 0; tn < TN; ++tn) acc[tm][tn] = mfma_main(af[tm], bf[tn], acc[tm][tn]);
   };
   if (KC % RING == 0) {
     // fast path: no conditionals around the loads in the steady state, so the compiler keeps exact
@@ -660,7 +628,7 @@ __device__ __forceinline__ void fwd_hidden_pack(f32x16 (&acc)[4][TN], const floa
       }
     });
     if (act_is_sign_based<ACT>() && sign_dst) {
-      if constexpr (TN == 2 && RG_SIGN_STORE16) {
+      if constexpr (TN == 2) {
         // a lane's four sign words (two per column tile) are contiguous: ONE 16-byte store per lane and layer — 1 KB per wave
         // instruction — instead of two 8-byte ones at a lane stride of 16 bytes
         if constexpr (tn == 0) { sg_prev0 = sg0; sg_prev1 = sg1; }
@@ -669,53 +637,6 @@ __device__ __forceinline__ void fwd_hidden_pack(f32x16 (&acc)[4][TN], const floa
         ((u32x2*)(sign_dst + sign_offset(mb_base >> 2, wave, lane, TN, NT * 32)))[tn] = u32x2{sg0, sg1};
       }
     }
-  });
-}
-
-// Non-saving forward with transposed accumulator tiles (wide_mainloop<.., SWAP>): a lane holds ONE batch row and 16 features
-// of a tile in four runs of four consecutive ones, so the bf16 pairs are column neighbours already and the LDS tile takes
-// them as 8-byte writes — no neighbour swap (DPP + v_perm per pair) and half the LDS write instructions of the
-// lane-per-column epilogue.  Nothing is saved in this layout (the fragment records backward and the weight gradient read
-// are lane-per-column): it serves save = 0 launches only.  Bias: 16 values per tile and half-wave, four 16-byte loads.
-template <int TN, int ACT>
-__device__ __forceinline__ void fwd_hidden_pack_swapped(f32x16 (&acc)[4][TN], const float* bias, int wave, int lane,
-                                                        unsigned (&PK)[4][TN][8]) {
-  lane = opaque(lane);
-  const int lg = lane >> 5;
-  static_for<0, TN>([&](auto tn_c) __attribute__((always_inline)) {
-    constexpr int tn = decltype(tn_c)::value;
-    const int f0 = (wave * TN + tn) * 32 + 4 * lg;
-    // the tile's 16 bias values (four runs of four features) are re-requested per row tile — 16-byte loads of a 2 KB
-    // vector every workgroup of the CU reads, L1-resident — so that they live across ONE tile: kept across the four row
-    // tiles of a column tile their 16 registers were what the 512-wide kernel (128 accumulators) spilled
-    static_for<0, 4>([&](auto tm_c) __attribute__((always_inline)) {
-      constexpr int tm = decltype(tm_c)::value;
-      sched_fence();  // one tile at a time: 16 accumulator registers die as 8 packed ones are born
-      f32x4 b4[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) b4[q] = bias ? *(const f32x4*)(bias + f0 + 8 * q) : f32x4{0.f, 0.f, 0.f, 0.f};
-      float v[16];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = act_t<ACT>(acc[tm][tn][r] + b4[r >> 2][r & 3]);
-      pack_tile(v, PK[tm][tn]);
-      pin_packed(PK[tm][tn]);
-    });
-    sched_fence();
-  });
-}
-
-template <int TN>
-__device__ __forceinline__ void store_packed_tiles_swapped(bf16_t* act, int pitch, const unsigned (&PK)[4][TN][8], int wave,
-                                                           int lane) {
-  const int lr = lane & 31, lg = lane >> 5;
-  static_for<0, TN>([&](auto tn_c) __attribute__((always_inline)) {
-    constexpr int tn = decltype(tn_c)::value;
-    static_for<0, 4>([&](auto tm_c) __attribute__((always_inline)) {
-      constexpr int tm = decltype(tm_c)::value;
-      bf16_t* row = act + (tm * 32 + lr) * pitch + (wave * TN + tn) * 32 + 4 * lg;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) *(uint2*)(row + 8 * q) = uint2{PK[tm][tn][2 * q], PK[tm][tn][2 * q + 1]};
-    });
   });
 }
 

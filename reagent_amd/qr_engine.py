@@ -120,11 +120,6 @@ class GroupedQR:
         self._B = -1
         self._side = None
         self.two_streams = os.environ.get("RG_QR_STREAMS", "1") != "0"  # the forward's two halves on two streams
-        # the native step's loss sum rides in the reduce launch of the trunk's weight gradient (round 6; 0 = on the weight gradients'
-        # side stream under the backward launch, rounds 4-5: one more fork of the main stream — a ~7 us marker gap — and a launch
-        # that waited 60 us for CUs in front of the side stream's weight gradient: same box C3 0.8095 / 0.8002 / 0.8094 ->
-        # 0.7752 / 0.7747 / 0.7756 ms, split-bf16 1.4777 / 1.4643 -> 1.4483 / 1.4481)
-        self.loss_in_reduce = os.environ.get("RG_QR_LOSS_IN_REDUCE", "1") != "0"
         self.wgrad_streams = os.environ.get("RG_QR_WGRAD_STREAMS", "1") != "0"  # the backward's two weight-gradient launches
         self.dense = os.environ.get("RG_QR_DENSE", "1") != "0"  # grouped spaces without per-group padding (GroupedSpace)
 
@@ -177,10 +172,8 @@ class GroupedQR:
         self.dz = torch.empty(R, ldz, **f32)
         self.loss_partials = torch.empty(R, **f32)
         # batch splits of a group's head weight gradient: A groups x 2 k-groups x splits workgroups, run beside the trunk's
-        # weight gradient on the other stream.  Round 4, same box, C3 step in ms (bf16 / split-bf16): 16 splits 0.936 / 1.566,
-        # 8 (rounds 2-4) 0.916 / 1.553, **4: 0.896 / 1.542**, 2: 0.902 / 1.564 — half the partial slabs (26 MB) and half of
-        # their reduce launch against workgroups twice as long (`profiles/scripts/gpu_batch21.sh`)
-        self.splits = int(os.environ.get("RG_QR_HEAD_SPLITS", "4"))
+        # weight gradient on the other stream (round 4's A/B of 2-16 splits: profiles/NOTES_r01_r05.md)
+        self.splits = 4
         nb = L.lib().rg_group_head_wgrad_workspace_bytes(A, N, H, self.splits)
         self.wg_ws = torch.empty(nb // 4, **f32)
         self._B = B
@@ -233,20 +226,9 @@ class GroupedQR:
                             tr._f32c(b.not_terminal).reshape(-1), tr.gamma, gamma_exp, tr.quantiles.reshape(-1), B, self.N,
                             self.dz, self.loss_partials)
         # the rows' loss terms (padding rows: 0) summed in fixed order.  Nothing on the device waits for the loss, so in the native
-        # step the sum leaves the critical path: in the reduce launch of the trunk's weight gradient (loss_in_reduce, the default)
-        # — or on the weight gradients' side stream, under the backward launch (joined where fused_backward_grouped joins it).
+        # step the sum leaves the critical path: it rides in the reduce launch of the trunk's weight gradient.
         # (Rounds 2-3: per-tile sums + their sum, two launch-bound launches = 13 us between the loss head and the backward.)
-        if getattr(tr, "_loss_tail_wanted", False) and state.is_cuda and self.wgrad_streams and not self.loss_in_reduce:
-            from .engine import side_stream
-
-            side = side_stream(dev)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                ops.reduce_sum(self.loss_partials, self.loss_partials.numel(), 1.0, tr._loss)
-                # whoever hands tr._loss out waits for THIS (train_step_native's finally): the join inside
-                # fused_backward_grouped only happens when that backward runs, with two_streams on
-                tr._loss_side_event = side.record_event()
-        elif getattr(tr, "_loss_tail_wanted", False):
+        if getattr(tr, "_loss_tail_wanted", False):
             tr._loss_tail = (self.loss_partials, 1.0, tr._loss)
         else:
             ops.reduce_sum(self.loss_partials, self.loss_partials.numel(), 1.0, tr._loss)

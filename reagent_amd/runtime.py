@@ -18,7 +18,6 @@ tails and slows them more than it hides; it is therefore OFF by default and kept
 1.237-1.241 against 1.179-1.181.  Two kernels sharing the memory system plus two cross-stream waits per step cost more
 than the 40 us they hide; not kept.)
 """
-import os
 from typing import Optional
 
 import torch
@@ -410,8 +409,6 @@ class OfflineDqnLoop(_GraphedLoop):
 
     def _cursor_protocol(self, dev):
         tr, rb = self.trainer, self.rb
-        if os.environ.get("RG_GRAPH_CURSOR", "1") == "0":  # same-box A/B switch: indices copied in before each replay
-            return None
         if not (self.fused_sampling and (self.fuse_norm or self.pre is None)) or rb._num_valid_indices != rb._replay_capacity:
             return None
         if getattr(tr, "_cpe", None) is not None or not isinstance(getattr(tr, "_fused_plan", None), dict):
@@ -480,11 +477,9 @@ class OfflinePolicyLoop(_GraphedLoop):
         if state_preprocessor is not None and not state_preprocessor.elementwise:
             raise NotImplementedError("normalize-on-gather needs a 1:1 column table")
 
-    # rg_replay_policy_batch (one launch) where the store has the shape it serves; RG_POLICY_SAMPLER=0: the three-launch path (A/B)
-    fused_sampler = os.environ.get("RG_POLICY_SAMPLER", "1") != "0"
-
     def make_batch(self, indices: Optional[torch.Tensor] = None) -> rlt.PolicyNetworkInput:
-        if self.fused_sampler and hasattr(self.rb, "sample_policy_input"):
+        # rg_replay_policy_batch (one launch) where the store has the shape it serves, else the three-launch path
+        if hasattr(self.rb, "sample_policy_input"):
             batch = self.rb.sample_policy_input(self.maker, self.batch_size, indices=indices, state_preprocessor=self.pre,
                                                 state_dtype=self.state_dtype)
             if batch is not None:

@@ -14,8 +14,6 @@ import logging
 from dataclasses import dataclass, field
 from typing import List, Optional, Tuple
 
-import os
-
 import torch
 
 from .. import _lib as L
@@ -451,15 +449,6 @@ class QStepCore(DQNTrainerBaseLightning):
     _loss_tail_wanted = False
     _loss_tail = None
 
-    _loss_side_event = None  # recorded after a loss sum that ran on the engine's side stream (qr_engine.py)
-
-    def _join_loss_side(self):
-        """the current stream waits for a loss sum enqueued on the side stream — whether or not the backward that
-        normally joins that stream ran"""
-        ev, self._loss_side_event = self._loss_side_event, None
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-
     def _take_loss_tail(self) -> dict:
         tail, self._loss_tail = self._loss_tail, None
         return {"tail_sum": tail} if tail is not None else {}
@@ -512,11 +501,8 @@ class QStepCore(DQNTrainerBaseLightning):
         for p in self._hip_params:
             p.grad = None
         deferred = defer_update and self._dp_group is not None
-        try:
-            with _NativeStep(self):
-                self._hip_backward(None, async_reduce=deferred)
-        finally:
-            self._join_loss_side()
+        with _NativeStep(self):
+            self._hip_backward(None, async_reduce=deferred)
         self._update_pending = True
         self._pending_batch = (training_batch if getattr(self, "_cpe", None) is not None or self._q_has_batch_norm()
                                else None)
@@ -541,12 +527,9 @@ class QStepCore(DQNTrainerBaseLightning):
             self._loss_tail_wanted = False
         for p in self._hip_params:
             p.grad = None
-        try:
-            with _NativeStep(self):
-                self._qs.backward(self._dq, self._xs_t, self._dw, self._db, **self._take_loss_tail())
-                publish_gradients(self._slab, self._hip_params)
-        finally:
-            self._join_loss_side()
+        with _NativeStep(self):
+            self._qs.backward(self._dq, self._xs_t, self._dw, self._db, **self._take_loss_tail())
+            publish_gradients(self._slab, self._hip_params)
         return loss
 
     @torch.no_grad()
@@ -577,8 +560,6 @@ class QStepCore(DQNTrainerBaseLightning):
         grouped = qs if isinstance(qs, GroupedQR) else None
         if grouped is not None:
             qs, ts = grouped.online.st, grouped.target.st
-            if self._fused_plan is None and os.environ.get("RG_QR_FUSED_UPDATE", "1") == "0":  # same-box A/B switch
-                self._fused_plan = False
         plan = self._fused_plan
         if plan is None:
             from ..optimizer import FusedAdam

@@ -21,7 +21,6 @@ get_log_prob: identical values, not repeated here).
 """
 import copy
 import math
-import os
 from typing import List, Optional
 
 import numpy as np
@@ -219,7 +218,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             assert self.value_network is not None
         self.backprop_through_log_prob = backprop_through_log_prob
         self.minibatch_size = minibatch_size
-        self.use_fused_update = os.environ.get("RG_SAC_FUSED_UPDATE", "1") != "0"  # engine.FusedUpdate in the native step
+        self.use_fused_update = True  # engine.FusedUpdate in the native step
         self._ws_batch = -1
         self._alpha_dev = None
         self._dp_group, self._dp_world = None, 1

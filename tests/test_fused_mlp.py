@@ -337,7 +337,7 @@ def test_dx_only_backward_of_a_frozen_stack(backend, prec, acts):
 @pytest.mark.parametrize("prec", [L.PREC_BF16, L.PREC_BF16X3])
 @pytest.mark.parametrize("n_out,batch", [(16, 256), (16, 200), (1, 256), (1, 130), (3, 128), (8, 192)])
 def test_thin_output_layer_store_forms_agree_bit_for_bit(backend, prec, n_out, batch):
-    """RG_OUT_ROWSTORE (round 5): a thin output layer's result leaves as whole 16-byte pieces through LDS — the tile's block as one
+    """The row store (round 5): a thin output layer's result leaves as whole 16-byte pieces through LDS — the tile's block as one
     run for a dense output and a full tile (a critic's single column), whole rows where N % 4 == 0 — and straight from the
     accumulators otherwise (a misaligned base, a row pitch that is no multiple of 4 floats, the last partial tile of a dense
     output).  Which form runs is decided per workgroup from the output's address and pitch; the VALUES must not depend on it:
