@@ -57,14 +57,18 @@ def frac_beyond(t, g, key, tol=2e-5):
     return float(((digest(t) - g.t(key)).abs() > tol).double().mean())
 
 
+def rel_errs(got, ref):
+    """(max|d| / max|ref|, ||d|| / ||ref||) of one tensor in float64: the first sees an error confined to a tile or a
+    few rows, the second one spread over the whole tensor"""
+    r = ref.detach().cpu().double()
+    d = got.detach().cpu().double().reshape(r.shape) - r
+    return (d.abs().max() / r.abs().max().clamp_min(1e-30)).item(), (d.norm() / r.norm().clamp_min(1e-30)).item()
+
+
 def grad_err(grads, g, prefix):
     """max over the tensors of max|dg| / max|g_ref| on the digests — the backward pass against what the
     reference's autograd handed its optimizer (well conditioned, unlike post-Adam weights)"""
-    worst_rel = 0.0
-    for i, gr in enumerate(grads):
-        ref = g.t(f"{prefix}{i}")
-        worst_rel = max(worst_rel, ((digest(gr) - ref).abs().max() / ref.abs().max().clamp_min(1e-30)).item())
-    return worst_rel
+    return max(rel_errs(digest(gr), g.t(f"{prefix}{i}"))[0] for i, gr in enumerate(grads))
 
 
 # Gradient bounds (relative to the tensor's largest entry), ~3x what the MI355X measures.  fp32: rounding only.

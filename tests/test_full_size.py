@@ -6,10 +6,13 @@ on the MI355X, checked through properties that do not need a CPU oracle of that 
   * the fused bf16 stack agrees with fp32 matmuls on the same weights within the bf16 bound, forward
     and backward (cosine of the full gradient);
   * the whole training step is deterministic (two runs from the same seed leave identical bits) and
-    its loss decreases on a fixed batch.
+    its loss decreases on a fixed batch;
+  * C2 / C3 / C4 steps against oracle/restated.py (C3 through its row-chunked pair loss): every gradient, both Adam
+    moments, the targets, SAC's temperature; the C2 stack against tests/test_fused_mlp.py's float64 statements.
 """
 import pytest
 import torch
+from test_baseline_shapes import rel_errs
 
 pytestmark = pytest.mark.gpu
 
@@ -366,3 +369,279 @@ def test_c4_step_against_the_oracle_at_full_size(monkeypatch):
     assert out["batch"] == B and out["gather_fields_bit_exact"], out
     assert out["max_abs_dlogits"] <= 1e-4 and out["rel_dloss"] <= 1e-4, out
     assert out["meets_north_star"] and out["ok"], out
+
+
+# ---- the full-size steps' gradients, Adam moments and targets against the oracle ---------------------------------------
+# The parity tests above bound Q-values, the loss and the weights after Adam.  Adam's first step moves a weight by
+# lr * g / (|g| + 1e-8), i.e. by +-lr whatever |g| is, and scaling every gradient by one factor leaves m / sqrt(v) unchanged
+# later: post-Adam weights see the SIGN of the gradient only.  What the backward pass computed is held here directly — every
+# gradient tensor (max-abs error over the tensor's largest entry, which sees a wrong tile or row slab, and the norm-relative
+# error, which sees an error spread over the tensor) and both Adam moments, which carry the gradient's magnitude — on the
+# launch plans the benchmark runs (B = 65 536; the uneven weight-gradient plan of rg_mlp_wgrad_fused applies to C2's stack).
+LR, TAU = 1e-3, 1e-3
+STEPS = {"c2": 2, "c3": 2, "c4": 2}  # oracle steps per config; the second is checked in the accurate modes
+
+
+def flagged(got, want, bound):
+    """indices of the tensors whose (max|d| / max|want|, ||d|| / ||want||) exceed bound = (max_rel, norm_rel)"""
+    return [i for i, (a, b) in enumerate(zip(got, want)) if any(e > t for e, t in zip(rel_errs(a, b), bound))]
+
+
+def worst(got, want):
+    e = [rel_errs(a, b) for a, b in zip(got, want)]
+    return max(x for x, _ in e), max(y for _, y in e)
+
+
+# Bounds (max_rel, norm_rel) at ~3x the MI355X figures printed by the test below (-s): `grad` for the gradients and exp_avg
+# (= 0.1 g) after the first step, `step2` for exp_avg after the second (it starts from weights that differ by 2 lr at the
+# sign-undetermined elements); exp_avg_sq (= 1e-3 g^2 first) gets twice the relative error.  Split-bf16 at 65 536 rows sits
+# well inside GRAD_TOL (3e-3 at 2048 rows, tests/test_baseline_shapes.py): a flipped ReLU mask weighs 1/B of a coherent sum.
+# The SAC actor's gradient is ill-conditioned (that file's header): its own bound, and 1 - cosine.
+STEP_BOUND = {
+    ("c2", "f32"): dict(grad=(1e-4, 4e-5), step2=(4e-4, 5e-4)),  # measured 2.9e-5 / 1.4e-5; 1.2e-4 / 1.5e-4
+    ("c2", "bf16x3"): dict(grad=(8e-4, 5e-4), step2=(4e-3, 2.5e-3)),  # 2.3e-4 / 1.6e-4; 1.1e-3 / 7.5e-4
+    ("c2", "bf16"): dict(grad=(2e-2, 2e-2)),  # 6.8e-3 / 5.9e-3: bf16 operands, activations and dZ
+    ("c3", "bf16x3"): dict(grad=(2.5e-4, 1.5e-4), step2=(2.5e-4, 2e-4)),  # 6.9e-5 / 4.3e-5; 6.0e-5 / 5.3e-5
+    ("c3", "bf16"): dict(grad=(1.5e-2, 1e-2)),  # 4.3e-3 / 3.0e-3
+    ("c4", "bf16x3"): dict(grad=(5e-4, 3.5e-4), step2=(2.5e-3, 6e-4),  # critics 1.6e-4 / 1.0e-4; 7.9e-4 / 1.8e-4
+                           actor=(1.5e-3, 1.5e-3), actor_step2=(2e-3, 2e-3), actor_cos=2e-7),  # 4.1e-4 / 4.1e-4, 4e-8; 6.3e-4 / 6.8e-4
+    ("c4", "bf16"): dict(grad=(1.5e-2, 1.5e-2), actor=(2e-2, 2e-2), actor_cos=3e-5),  # 4.8e-3 / 4.5e-3; 5.5e-3 / 5.6e-3, 1e-5
+}
+
+
+def _args(config, precision, monkeypatch):
+    import sys
+
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--config", config, "--precision", precision, "--parity-batch", str(B)])
+    return bench.parse()
+
+
+def _draws(args, steps):
+    """bench.parity_check's draws: indices from Generator(11), then SAC's two noises; a second step continues the stream"""
+    g = torch.Generator().manual_seed(11)
+    out = []
+    for _ in range(steps):
+        idx = torch.randint(args.capacity, (B,), generator=g)
+        noise = (torch.randn(B, args.actions, generator=g), torch.randn(B, args.actions, generator=g)) if args.algo == "sac" else None
+        out.append((idx, noise))
+    return out
+
+
+def _clone(ts):
+    return [t.detach().clone() for t in ts]
+
+
+def _oracle_run(args, init, cols, norm):
+    """The oracle's steps on the draws above (precision-independent): per step its gradients, Adam moments, weights and
+    targets after the step, loss(es); QR-DQN also the logged action's quantiles and next-state means before the step."""
+    import bench
+
+    o = bench.make_oracle(args, init)
+    recs = []
+    for idx, noise in _draws(args, STEPS[args.config]):
+        b = bench.cpu_batch(args, cols, norm, idx)
+        rec = {}
+        if args.algo == "sac":
+            r = o.step(b, *noise)
+            rec["grads"] = {n: _clone(r[f"{n}_grads"]) for n in ("q1", "q2", "actor")}
+            rec["moments"] = {n: [(op.state[p]["exp_avg"].clone(), op.state[p]["exp_avg_sq"].clone()) for p in ps]
+                              for n, op, ps in (("q1", o.opt_q1, o.q1), ("q2", o.opt_q2, o.q2), ("actor", o.opt_actor, o.actor),
+                                                ("alpha", o.opt_alpha, [o.log_alpha]))}
+            rec["weights"] = {n: _clone(ps) for n, ps in dict(actor=o.actor, q1=o.q1, q2=o.q2).items()}
+            rec["targets"] = {"q1": _clone(o.q1_t), "q2": _clone(o.q2_t)}
+            rec["log_alpha"] = o.log_alpha.detach().clone()
+            rec["log_alpha_grad"] = r["log_alpha_grad"]
+            rec["loss"] = {k: float(r[k]) for k in ("q1_loss", "q2_loss", "actor_loss", "alpha_loss")}
+        else:
+            if args.algo == "qrdqn":
+                with torch.no_grad():
+                    rec["next_mean"] = o.net(o.params, b["next_state"]).mean(dim=2)
+            r = o.step(b)
+            rec["grads"] = {"q": _clone(r["grads"])}
+            rec["moments"] = {"q": [(o.opt.state[p]["exp_avg"].clone(), o.opt.state[p]["exp_avg_sq"].clone()) for p in o.params]}
+            rec["weights"] = {"q": _clone(o.params)}
+            rec["targets"] = {"q": _clone(o.target)}
+            rec["loss"] = {"loss": r["loss"].item()}
+            if args.algo == "qrdqn":
+                rec["current_qf"], rec["action"] = r["current_qf"], b["action"].argmax(1)
+        recs.append(rec)
+    return recs
+
+
+@pytest.fixture(scope="module")
+def oracle_steps():
+    """config -> (init, cols, records): one oracle run per config, shared by its precision modes"""
+    return {}
+
+
+def _shared_oracle(cache, args, init, cols, norm):
+    if args.config in cache:
+        init0, cols0, recs = cache[args.config]
+        # the oracle's step does not depend on the precision mode: only the inputs must be the same
+        assert all(torch.equal(a, b) for n0, n1 in zip(init0, init) for a, b in zip(n0, n1))
+        assert sorted(cols0) == sorted(cols) and all(torch.equal(cols0[k], cols[k]) for k in cols)
+        return recs
+    recs = _oracle_run(args, init, cols, norm)
+    cache.clear()  # (one config's shard at a time on the host)
+    cache[args.config] = (init, cols, recs)
+    return recs
+
+
+def _device_state(args, trainer):
+    """gradients / Adam moments / weights / targets of the trainer after a step, in the oracle record's layout"""
+    opts = trainer.native_optimizers()
+    if args.algo == "sac":
+        nets = dict(q1=trainer.q1_network, q2=trainer.q2_network, actor=trainer.actor_network)
+        grads = {n: _clone(trainer._e[n]["slab"].grad_views()) for n in ("q1", "q2", "actor")}
+        moments = {n: [(opts[i].state[p]["exp_avg"].clone(), opts[i].state[p]["exp_avg_sq"].clone()) for p in nets[n].parameters()]
+                   for i, n in enumerate(("q1", "q2", "actor"))}
+        st = opts[3].state[trainer.log_alpha]
+        moments["alpha"] = [(st["exp_avg"].clone(), st["exp_avg_sq"].clone())]
+        weights = {n: _clone(net.parameters()) for n, net in nets.items()}
+        targets = {"q1": _clone(trainer.q1_network_target.parameters()), "q2": _clone(trainer.q2_network_target.parameters())}
+    else:
+        grads = {"q": _clone(trainer._slab.grad_views())}
+        moments = {"q": [(opts[0].state[p]["exp_avg"].clone(), opts[0].state[p]["exp_avg_sq"].clone())
+                         for p in trainer.q_network.parameters()]}
+        weights = {"q": _clone(trainer.q_network.parameters())}
+        targets = {"q": _clone(trainer.q_network_target.parameters())}
+    return grads, moments, weights, targets
+
+
+@pytest.mark.parametrize("config,precision", [("c2", "f32"), ("c2", "bf16x3"), ("c2", "bf16"), ("c3", "bf16x3"), ("c3", "bf16"),
+                                              ("c4", "bf16x3"), ("c4", "bf16")])
+def test_full_size_step_gradients_and_moments_against_the_oracle(config, precision, oracle_steps, monkeypatch):
+    """C2 / C3 / C4 at B = 65 536 driven as bench.parity_check drives them (bench.py is the yardstick and does not change, so
+    its flow is restated: bench.build's shard and initial weights, its index / noise draws, loop.step + loop.flush or SAC's
+    train_step_native), against oracle/restated.py on the same batch (C3: the row-chunked pair loss): every gradient tensor,
+    exp_avg / exp_avg_sq of every parameter, the targets after the soft update, SAC's log_alpha and its float64 moments; C3
+    also the logged action's quantiles of every row and the next-state per-action means.  The accurate modes take a second
+    step: moments again, and the weights by the s >= 1 rule of tests/test_baseline_shapes.py."""
+    import bench
+
+    args = _args(config, precision, monkeypatch)
+    dev = torch.device("cuda:0")
+    loop, trainer, init, cols, norm = bench.build(args, dev, 0, batch=B)
+    recs = _shared_oracle(oracle_steps, args, init, cols, norm)
+    bound = STEP_BOUND[(config, precision)]
+    accurate = precision in ("f32", "bf16x3")
+    steps = len(recs) if accurate else 1
+    fails = []
+
+    def check(name, value, limit):
+        print(f"  {name:<40} {value:.3e}  (bound {limit:.1e})")
+        if not value <= limit:
+            fails.append((name, value, limit))
+
+    for s, ((idx, noise), ref) in enumerate(zip(_draws(args, steps), recs)):
+        print(f"\n[full size {config} {precision} step {s}]")
+        if args.algo == "sac":
+            out = trainer.train_step_native(loop.make_batch(idx.to(dev)), *noise)
+            got_loss = {k: float(out[k]) for k in ref["loss"]}
+        else:
+            got_loss = {"loss": loop.step(idx.to(dev)).item()}
+            loop.flush()
+        torch.cuda.synchronize()
+        for k, v in got_loss.items():
+            check(f"rel d{k}", abs(v - ref["loss"][k]) / max(abs(ref["loss"][k]), 1e-3), 1e-4 if accurate else 3e-2)
+        if args.algo == "qrdqn":
+            gq = trainer._gq_active
+            assert gq is not None and gq.x3 == (precision == "bf16x3")
+            rowmap, key = gq.sp_cur.rowmap.cpu().long(), gq.key_cur.cpu().long()
+            live = rowmap >= 0
+            rows = rowmap[live]
+            assert int(live.sum()) == B and torch.equal(key[rows], ref["action"][rows])
+            zq = (gq.z.cpu()[live][:, :args.atoms] - ref["current_qf"][rows]).abs().max().item()
+            zm = (gq.qbar_next.cpu() - ref["next_mean"]).abs().max().item()
+            qtol = 1e-4 if accurate else 6e-2  # bf16: test_baseline_shapes.py's quantile bound (measured 3.8e-2)
+            check("max|dquantile| (logged action, all rows)", zq, qtol if s == 0 else 1e-2)
+            check("max|dmean| (next state, all actions)", zm, qtol if s == 0 else 1e-2)
+        grads, moments, weights, targets = _device_state(args, trainer)
+        for n, want in ref["grads"].items():
+            tol = bound["actor"] if n == "actor" else bound["grad"]
+            mx, nr = worst(grads[n], want)
+            if s == 0:
+                check(f"{n} grad max|d|/max|g|", mx, tol[0])
+                check(f"{n} grad ||d||/||g||", nr, tol[1])
+                if n == "actor":  # ill-conditioned (tests/test_baseline_shapes.py header): its direction as well
+                    cat = lambda ts: torch.cat([t.reshape(-1).double().cpu() for t in ts])  # noqa: E731
+                    cos = torch.nn.functional.cosine_similarity(cat(grads[n]), cat(want), dim=0).item()
+                    check("actor grad 1 - cosine", 1.0 - cos, bound["actor_cos"])
+            else:
+                print(f"  {n} grad max|d|/max|g| {mx:.3e} ||d||/||g|| {nr:.3e} (printed: starts from direction-flipped weights)")
+        for n, want in ref["moments"].items():
+            got = moments[n]
+            m1 = worst([m for m, _ in got], [m for m, _ in want])
+            m2 = worst([v for _, v in got], [v for _, v in want])
+            tol = bound[("actor" if n == "actor" else "grad") if s == 0 else ("actor_step2" if n == "actor" else "step2")]
+            check(f"{n} exp_avg max|d|/max", m1[0], tol[0])
+            check(f"{n} exp_avg ||d||/||m||", m1[1], tol[1])
+            check(f"{n} exp_avg_sq max|d|/max", m2[0], 2 * tol[0])
+            check(f"{n} exp_avg_sq ||d||/||v||", m2[1], 2 * tol[1])
+        flip = 2.0 * (s + 1) * LR * 1.05  # Adam moves a weight by +-lr whatever |g|: sign-undetermined weights differ by 2 lr a step
+        for n, want in ref["weights"].items():
+            d = [(a.cpu() - b).abs() for a, b in zip(weights[n], want)]
+            frac = sum((x > 2e-5).sum().item() for x in d) / sum(x.numel() for x in d)
+            check(f"{n} max|dW|", max(x.max().item() for x in d), flip)
+            check(f"{n} frac |dW| > 2e-5", frac, (0.02 if s == 0 else 0.1) if accurate else 1.0)
+        for n, want in ref["targets"].items():
+            dt = max((a.cpu() - b).abs().max().item() for a, b in zip(targets[n], want))
+            check(f"{n} target max|dW|", dt, TAU * flip + 1e-7)
+        if args.algo == "sac":
+            check("|dlog_alpha|", abs(trainer.log_alpha.item() - ref["log_alpha"].item()), 1e-6)
+    assert not fails, fails
+
+
+# (max_rel, norm_rel) of the stack's results at full size: tests/test_fused_mlp.py's norm bounds (bf16 2e-3 output, 5e-3 the
+# rest; split-bf16 2e-5 / 3e-5), max-abs over max at ~3x the MI355X figure
+STACK_BOUND = {
+    "bf16": dict(out=(6e-3, 2e-3), grad=(2.5e-2, 5e-3), dx=(1.5e-1, 5e-3)),  # measured (ReLU) out 1.8e-3, dW 8.1e-3, dx 5.1e-2
+    "bf16x3": dict(out=(3e-5, 2e-5), grad=(5e-5, 3e-5), dx=(5e-5, 3e-5)),  # (tanh) out 1.0e-5, dW / db 1.6e-5, dx 1.3e-5
+}
+
+
+@pytest.mark.parametrize("precision,act", [("bf16", "relu"), ("bf16", "tanh"), ("bf16x3", "tanh")])
+def test_fused_stack_against_the_float64_statements_at_full_size(precision, act):
+    """C2's stack (128-512-512-512-16) at B = 65 536 — the launch plans of the benchmark, among them the uneven two-entry
+    weight-gradient plan that only this shape meets — against tests/test_fused_mlp.py's float64 statements: bf16 against
+    _ref (bf16 rounding at the kernels' points), split-bf16 against _ref64 (exact).  Forward, and dW / db of every layer and
+    dx, by norm (test_fused_mlp's bounds) and by max-abs over max (a wrong tile or row slab); split-bf16 output also within
+    1e-4 max-abs.  Split-bf16 runs the same shape with tanh hidden layers: with ReLU and a random dout the float64 gradient
+    of 65 536 rows is a sum with sqrt(B)-fold cancellation in which every ReLU mask that the arithmetic's own rounding
+    flips weighs in full — exact fp32 itself is 5e-4 (norm) from float64 there — while tanh has no kink (fp32: 7e-7)."""
+    import reagent_amd._lib as L
+    import test_fused_mlp as T
+    from reagent_amd.engine import FusedMLP, make_stack
+
+    dev = torch.device("cuda")
+    acts = [act] * 3 + ["linear"]
+    ws, bs = T._net([S, H, H, H, A], acts, 1, dev)
+    st = make_stack(ws, bs, [L.ACT[a] for a in acts], L.PREC_BF16 if precision == "bf16" else L.PREC_BF16X3)
+    assert isinstance(st, FusedMLP) and st.x3 == (precision == "bf16x3")
+    st.set_need_input_grad(True)
+    st.stage_weights(need_transposed=True)
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn(B, S, generator=g).to(dev)
+    dout = (torch.randn(B, A, generator=g) / B).to(dev)
+    out = torch.zeros(B, A, device=dev)
+    xc, xt = st.stage_input(x, True)
+    st.forward(xc, out, save=True)
+    dw = [torch.zeros_like(w) for w in ws]
+    db = [torch.zeros_like(b) for b in bs]
+    dx = torch.zeros(B, S, device=dev)
+    st.backward(dout, xt, dw, db, dx32=dx)
+    torch.cuda.synchronize()
+    ref_out, ref_dw, ref_db, ref_dx = (T._ref if precision == "bf16" else T._ref64)(ws, bs, acts, x, dout)
+    bound = STACK_BOUND[precision]
+    got = dict(out=out, dx=dx, **{f"dW{l}": dw[l] for l in range(4)}, **{f"db{l}": db[l] for l in range(4)})
+    want = dict(out=ref_out, dx=ref_dx, **{f"dW{l}": ref_dw[l] for l in range(4)}, **{f"db{l}": ref_db[l] for l in range(4)})
+    errs = {k: rel_errs(got[k], want[k]) for k in got}
+    print(f"\n[full-size stack {precision} {act}] (max|d|/max, ||d||/||ref||): "
+          + "  ".join(f"{k} ({m:.2e}, {n:.2e})" for k, (m, n) in errs.items()))
+    for k, e in errs.items():
+        tol = bound[k if k in ("out", "dx") else "grad"]
+        assert e[0] <= tol[0] and e[1] <= tol[1], (k, e, tol)
+    if precision == "bf16x3":
+        assert (out.double().cpu() - ref_out).abs().max() <= 1e-4

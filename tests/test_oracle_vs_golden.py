@@ -64,6 +64,40 @@ def test_qrdqn_oracle_matches_reference(name):
             torch.testing.assert_close(p, g.t(f"step{s}_target_{i}"), **TIGHT)
 
 
+@pytest.mark.parametrize("name", ["qrdqn_double", "qrdqn_single_sarsa", "qrdqn_dueling", "baseline_c3"])
+def test_row_chunked_qrdqn_oracle_equals_the_unchunked_one(name):
+    """QRDQNOracle's row-chunked pair loss (what it runs above 8192 rows, where the (N, B, N) tensor does not fit the host)
+    forced onto these batches with a ragged last chunk, against the unchunked formula that the goldens pin: loss within
+    1e-6 relative, every gradient within 1e-6 of its tensor's largest entry, post-step weights and targets within TIGHT"""
+    from reagent_amd import synthetic
+
+    g = Golden(name)
+    c = g.cfg
+    if name == "baseline_c3":  # big tensors are digests in this fixture: regenerate the inputs from their seeds
+        dims = [c["state_dim"]] + c["sizes"] + [c["num_actions"] * c["num_atoms"]]
+        init = synthetic.fc_init(dims, _acts(c), c["init_seed"])
+        batches = [synthetic.dqn_batch(c["batch"], c["state_dim"], c["num_actions"], seed=700 + s,
+                                       p_impossible=c["p_impossible"]) for s in range(c["steps"])]
+        assert torch.equal(batches[0]["state"].reshape(-1)[::61], g.t("step0_batch_state"))
+    else:
+        init = g.seq("init_param_")
+        batches = [g.batch(s) for s in range(c["steps"])]
+    rows = 7 if c["batch"] < 100 else 100
+    assert c["batch"] % rows != 0  # a ragged last chunk
+    kw = dict(num_actions=c["num_actions"], num_atoms=c["num_atoms"], gamma=c["rl"]["gamma"],
+              tau=c["rl"]["target_update_rate"], double_q=c["double_q"], maxq=c["rl"]["maxq_learning"], lr=c["lr"],
+              dueling=c.get("dueling", False))
+    plain = R.QRDQNOracle(init, init, _acts(c), **kw)
+    chunked = R.QRDQNOracle(init, init, _acts(c), chunk_rows=rows, **kw)
+    for b in batches:
+        want, got = plain.step(b), chunked.step(b)
+        assert abs(got["loss"].item() - want["loss"].item()) <= 1e-6 * abs(want["loss"].item())
+        for gr, wr in zip(got["grads"], want["grads"]):
+            assert (gr - wr).abs().max() <= 1e-6 * wr.abs().max()
+        for p, q in zip(chunked.params + chunked.target, plain.params + plain.target):
+            torch.testing.assert_close(p.detach(), q.detach(), **TIGHT)
+
+
 def test_sac_oracle_matches_reference():
     g = Golden("sac_twin")
     c = g.cfg
