@@ -214,6 +214,10 @@ typedef struct {
   const float* sum_in;
   float* sum_out;
   double sum_scale;
+  /* ABI 12: sum_run > 1 — sum_in holds sum_n per-wave sums (rg_dqn_online_pair_forward's loss_wave_sums); each run of
+   * sum_run of them is first added in order into one value (what rg_dqn_head adds into one partial per 256 rows) and the
+   * values are then summed as above: the same adds in the same order as rg_dqn_head's partials.  0 / 1: as before. */
+  int32_t sum_run;
 } rg_mlp_desc; /* host struct */
 
 int rg_mlp_fused_supported(const rg_mlp_desc* d);
@@ -552,6 +556,25 @@ int rg_dqn_head(const float* q, const float* qn_online, const float* qn_target, 
                 int num_actions, int double_q, int loss_type, float* dq, float* loss_partials,
                 float* next_q, int64_t* next_idx, float* q_sel, rg_stream_t stream);
 
+/* ABI 12 — the online network's two forwards of a DQN step and the TD head in ONE launch (bf16 fused stacks with a
+ * 16-wide output): a workgroup takes rows [128 t, 128 t + 128) of next_state (not saving; -> qn_online) AND of state
+ * (saving as rg_mlp_forward_fused(save = 1) does; -> q) — alternate workgroups in alternate order, so that the saving
+ * passes' store bursts do not all fall on the same moment — and finishes with rg_dqn_head's arithmetic for those rows,
+ * reading qn_target (the target network's forward runs before this launch) and the head's other operands as rg_dqn_head
+ * does.  Every output (q, qn_online, the saved fragments and sign planes, dq, next_q, next_idx, q_sel) has the bits of
+ * rg_mlp_forward_fused x 2 + rg_dqn_head.  The loss leaves as one sum per wave, loss_wave_sums
+ * [rg_dqn_pair_wave_sums(B)] (16 rows each, rg_dqn_head's lane order): rg_mlp_wgrad_fused (rg_mlp_desc.sum_run = 16) or
+ * rg_reduce_sum_runs(run = 16) finishes it with the adds of rg_dqn_head + rg_reduce_sum.
+ * q, qn_online, qn_target, action, next_mask, dq: [B, 16] fp32 contiguous, 16-byte aligned.  RG_EUNSUPPORTED for
+ * anything else (split-bf16, grouped or two-panel stacks, other widths): callers then run the three launches. */
+int rg_dqn_pair_wave_sums(int batch);
+int rg_dqn_online_pair_forward(const rg_mlp_desc* d, const void* state, int state_dtype, int64_t ld_state,
+                               const void* next_state, int next_state_dtype, int64_t ld_next_state, int batch, float* q,
+                               float* qn_online, const float* qn_target, const float* action, const float* next_mask,
+                               const float* reward, const float* reward_boosts, const float* not_terminal, double gamma,
+                               const float* gamma_exponent, int double_q, int loss_type, float* dq, float* loss_wave_sums,
+                               float* next_q, int64_t* next_idx, float* q_sel, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */
@@ -764,6 +787,9 @@ int rg_add_cols(const float* a, int64_t lda, const float* b, int64_t ldb, int ba
 
 /* out[0] = scale * sum_i in[i], summed in index order by one workgroup (deterministic). */
 int rg_reduce_sum(const float* in, int n, float scale, float* out, rg_stream_t stream);
+/* ABI 12: the same over values that are ordered sums of runs of `run` consecutive inputs (the last run may be short):
+ * rg_reduce_sum_runs(wave sums of rg_dqn_online_pair_forward, n, 16, ..) == rg_reduce_sum(rg_dqn_head's partials, ..). */
+int rg_reduce_sum_runs(const float* in, int n, int run, float scale, float* out, rg_stream_t stream);
 
 /* ---- optimizer ---------------------------------------------------------------------------- */
 

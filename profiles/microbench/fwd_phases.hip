@@ -18,6 +18,17 @@ void grouped_bias_reduce_launch(const float*, const int*, int, int, float*, int,
 #include <cstdio>
 #include <vector>
 
+// argv[4] = S > 0 (round 7): only the workgroups with bit log2(S) of their index set save (S = 1: every other workgroup,
+// S = 8: every other group of 8), the rest run the non-saving forward — are the saving workgroups' PACK phases slow because
+// every CU stores at the same moment, or is it a per-CU limit?  The tables then cover the SAVING workgroups only.
+namespace rg {
+template <int TN, int NW, int PITCH>
+__global__ void RG_LAUNCH_BOUNDS(NW * 64, 1) fwd_some_save_kernel(MlpArgs saving, MlpArgs plain, int every) {
+  if ((int)blockIdx.x & every) mlp_fwd_fused_body<TN, NW, PITCH, false>(saving);
+  else mlp_fwd_fused_body<TN, NW, PITCH, false>(plain);
+}
+}  // namespace rg
+
 int main(int argc, char** argv) {
   using namespace rg;
   const int save = argc > 1 ? atoi(argv[1]) : 0;
@@ -47,12 +58,20 @@ int main(int argc, char** argv) {
   hipMemcpyToSymbol(HIP_SYMBOL(g_stamps), &stamps, sizeof(stamps));
   a.out_lds = argc > 3 ? atoi(argv[3]) : 0;  // argv[3] = 1: the output layer's weights resident in LDS (round 3)
   const size_t lds = (size_t)128 * 520 * 2 + (a.out_lds ? 32 * 512 : 0);
+  const int every = argc > 4 ? atoi(argv[4]) : 0;
+  MlpArgs plain = a;
+  plain.save = 0;
   hipFuncSetAttribute((const void*)mlp_fwd_fused_kernel<512 / (32 * FB_NW), FB_NW, 520>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipFuncSetAttribute((const void*)fwd_some_save_kernel<512 / (32 * FB_NW), FB_NW, 520>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  auto launch = [&] {
+    if (every) fwd_some_save_kernel<512 / (32 * FB_NW), FB_NW, 520><<<n_wg, FB_NW * 64, lds>>>(a, plain, every);
+    else mlp_fwd_fused_kernel<512 / (32 * FB_NW), FB_NW, 520><<<n_wg, FB_NW * 64, lds>>>(a);
+  };
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  for (int w = 0; w < 3; ++w) mlp_fwd_fused_kernel<512 / (32 * FB_NW), FB_NW, 520><<<n_wg, FB_NW * 64, lds>>>(a);
+  for (int w = 0; w < 3; ++w) launch();
   hipDeviceSynchronize();
   hipEventRecord(e0);
-  for (int r = 0; r < 20; ++r) mlp_fwd_fused_kernel<512 / (32 * FB_NW), FB_NW, 520><<<n_wg, FB_NW * 64, lds>>>(a);
+  for (int r = 0; r < 20; ++r) launch();
   hipEventRecord(e1); hipEventSynchronize(e1);
   float ms; hipEventElapsedTime(&ms, e0, e1);
   printf("forward NW=%d RING=%d save=%d: %.2f us/launch (stamps on), err=%d\n", FB_NW, MlpCfg<FB_NW>::RING, save, ms * 1e3 / 20, (int)hipGetLastError());
@@ -62,13 +81,18 @@ int main(int argc, char** argv) {
                             "L1 mainloop(K=512)", "L1 pack", "L1 barrier wait", "L1 LDS store+barrier",
                             "L2 mainloop(K=512)", "L2 pack", "L2 barrier wait", "L2 LDS store+barrier", "output layer", ""};
   double tot[NPH] = {0}, span = 0;
-  for (int g = 0; g < n_wg; ++g)
+  int n_counted = 0;
+  for (int g = 0; g < n_wg; ++g) {
+    if (every && !(g & every)) continue;  // the saving workgroups only
+    ++n_counted;
     for (int w = 0; w < NWV; ++w) {
       const unsigned long long* s = &h[((size_t)g * NWV + w) * NPH];
       for (int p = 1; p <= 14; ++p) tot[p] += (double)(s[p] - s[p - 1]);
       span += (double)(s[14] - s[0]);
     }
-  const double nw = (double)n_wg * NWV;
+  }
+  const double nw = (double)n_counted * NWV;
+  if (every) printf("only workgroups with (index & %d) save: the tables below cover those %d\n", every, n_counted);
   printf("workgroups %d, shader clock %.3f GHz (ticks of one round / launch time)\n", n_wg, (span / nw) * ((n_wg + 255) / 256) / (ms * 1e6 / 20));
   printf("avg s_memtime ticks per wave: %.0f\n", span / nw);
   for (int p = 1; p <= 14; ++p) printf("  %-22s %9.0f ticks  %5.1f %%\n", names[p], tot[p] / nw, 100.0 * tot[p] / span);
@@ -78,7 +102,7 @@ int main(int argc, char** argv) {
     for (int g = 0; g < n_wg; ++g)
       for (int w = 0; w < NWV; ++w) {
         const unsigned long long* s = &h[((size_t)g * NWV + w) * NPH];
-        if (!s[16]) continue;
+        if (!s[16] || (every && !(g & every))) continue;
         if (s[19]) { t19 += (double)(s[19] - s[18]); n19 += 1; }
         t[0] += (double)(s[16] - s[13]); t[1] += (double)(s[17] - s[16]); t[2] += (double)(s[18] - s[17]); t[3] += (double)(s[14] - s[18]);
       }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RG_LIB: another build of the same library (same-box A/B of compile-time kernel variants); default = the in-tree build
 LIB_PATH = os.environ.get("RG_LIB") or os.path.join(_HERE, "lib", "libreagent_hip.so")
 
-ABI_VERSION = 11  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
+ABI_VERSION = 12  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT = {"linear": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}
@@ -94,6 +94,7 @@ class MlpDesc(ctypes.Structure):
         ("sum_in", c_void_p),
         ("sum_out", c_void_p),
         ("sum_scale", ctypes.c_double),
+        ("sum_run", ctypes.c_int32),
     ]
 
 
@@ -232,6 +233,9 @@ SIGNATURES = {
     "rg_table_check_actions": (c_int, [ctypes.POINTER(DqnTable), c_void_p, c_int, c_void_p, c_void_p]),
     "rg_bcq_filter": (c_int, [c_void_p, c_int, c_int, c_d, c_void_p, c_void_p]),
     "rg_dqn_head_partials": (c_int, [c_int]),
+    "rg_dqn_pair_wave_sums": (c_int, [c_int]),
+    "rg_dqn_online_pair_forward": (c_int, [ctypes.POINTER(MlpDesc), c_void_p, c_int, c_i64, c_void_p, c_int, c_i64, c_int]
+                                   + [c_void_p] * 8 + [c_d, c_void_p, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "rg_dqn_head": (c_int, [c_void_p] * 8 + [c_d, c_void_p, c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "rg_cpe_head": (c_int, [c_void_p] * 9 + [ctypes.c_double, c_void_p, ctypes.c_double, c_int, c_int, c_int, c_int,
                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -258,6 +262,7 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "rg_add_cols": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "rg_reduce_sum": (c_int, [c_void_p, c_int, c_f, c_void_p, c_void_p]),
+    "rg_reduce_sum_runs": (c_int, [c_void_p, c_int, c_int, c_f, c_void_p, c_void_p]),
     "rg_adam_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_d, c_d, c_d, c_d, c_d,
                               c_d, c_d, c_d, c_void_p]),
     "rg_soft_update": (c_int, [c_void_p, c_void_p, c_i64, c_d, c_void_p]),

@@ -2,6 +2,7 @@
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
 #include "rg_reduce.h"
+#include "rg_dqn_head_row.h"
 
 namespace rg {
 
@@ -121,73 +122,25 @@ __global__ void __launch_bounds__(256 * G) dqn_head_lanes_kernel(
     const float* __restrict__ gamma_exponent, int batch, int double_q, int loss_type, float* __restrict__ dq,
     float* __restrict__ loss_partials, float* __restrict__ next_q_out, int64_t* __restrict__ next_idx_out,
     float* __restrict__ q_sel_out) {
-  constexpr int A = 4 * G, WAVES = 4 * G;
+  constexpr int A = 4 * G, WAVES = 4 * G;  // (WAVES: 256 rows of G lanes)
   __shared__ float scratch[WAVES];
   const int t = threadIdx.x, sub = t % G;
   const int b_raw = blockIdx.x * 256 + t / G;
   // rows past the end recompute the last row and store nothing: every lane takes part in the shuffles
   const bool live = b_raw < batch;
   const int b = live ? b_raw : batch - 1;
-  float loss = 0.f;
-  {
-    const long o = (long)b * A + sub * 4;
-    const f32x4 m4 = *(const f32x4*)(next_mask + o);
-    const f32x4 qt4 = *(const f32x4*)(qn_target + o);
-    const f32x4 qo4 = double_q ? *(const f32x4*)(qn_online + o) : qt4;
-    const f32x4 ac4 = *(const f32x4*)(action + o);
-    const f32x4 q4 = *(const f32x4*)(q + o);
-    float best = 0.f, best_t = 0.f, rb = 0.f, qs = 0.f;
-    int best_i = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float pen = -1e9f * (1.f - m4[e]);  // ACTION_NOT_POSSIBLE_VAL * (1 - mask)
-      const float qo = qo4[e] + pen, qt = qt4[e] + pen;
-      const float key = double_q ? qo : qt;
-      if (e == 0 || key > best) {
-        best = key;
-        best_t = qt;
-        best_i = sub * 4 + e;
-      }
-      if (reward_boosts) rb += ac4[e] * reward_boosts[sub * 4 + e];
-      qs += q4[e] * ac4[e];
-    }
-#pragma unroll
-    for (int off = 1; off < G; off <<= 1) {
-      const float ok = shfl_xor(best, off), ot = shfl_xor(best_t, off);
-      const int oi = shfl_xor(best_i, off);
-      if (ok > best || (ok == best && oi < best_i)) {
-        best = ok;
-        best_t = ot;
-        best_i = oi;
-      }
-      rb += shfl_xor(rb, off);
-      qs += shfl_xor(qs, off);
-    }
-    const float rew = reward[b] + rb;
-    const float disc = gamma_exponent ? powf(gamma, gamma_exponent[b]) : gamma;
-    const float target = rew + disc * (best_t * not_terminal[b]);
-    const float d = qs - target;
-    float g, row_loss;
-    if (loss_type == RG_LOSS_HUBER) {
-      const float ad = fabsf(d);
-      row_loss = ad < 1.f ? 0.5f * d * d : ad - 0.5f;
-      g = ad < 1.f ? d : (d > 0.f ? 1.f : -1.f);
-    } else {
-      row_loss = d * d;
-      g = 2.f * d;
-    }
-    g /= (float)batch;
-    if (live) *(f32x4*)(dq + o) = f32x4{g * ac4[0], g * ac4[1], g * ac4[2], g * ac4[3]};
-    if (live && sub == 0) {
-      loss = row_loss;
-      if (next_q_out) next_q_out[b] = best_t;
-      if (next_idx_out) next_idx_out[b] = best_i;
-      if (q_sel_out) q_sel_out[b] = qs;
-    }
-  }
+  const long o = (long)b * A + sub * 4;
+  const f32x4 m4 = *(const f32x4*)(next_mask + o);
+  const f32x4 qt4 = *(const f32x4*)(qn_target + o);
+  const f32x4 qo4 = double_q ? *(const f32x4*)(qn_online + o) : qt4;
+  const f32x4 ac4 = *(const f32x4*)(action + o);
+  const f32x4 q4 = *(const f32x4*)(q + o);
+  // (the row arithmetic lives in rg_dqn_head_row.h: the paired online forward of mlp_fused.hip runs the same code)
+  float loss = dqn_head_lanes_row<G>(m4, qt4, qo4, ac4, q4, sub, b, live, reward[b], reward_boosts, not_terminal[b], gamma,
+                                     gamma_exponent != nullptr, gamma_exponent ? gamma_exponent[b] : 0.f, batch, double_q,
+                                     loss_type, dq, next_q_out, next_idx_out, q_sel_out);
   // workgroup sum in a fixed order: wave shuffles, then the wave sums added in order
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) loss += shfl_xor(loss, off);
+  loss = dqn_head_wave_sum(loss);
   if ((t & 63) == 0) scratch[t >> 6] = loss;
   __syncthreads();
   if (t == 0) {
@@ -635,6 +588,13 @@ __global__ void reduce_sum_kernel(const float* __restrict__ in, int n, float sca
   if (threadIdx.x == 0) out[0] = s * scale;
 }
 
+__global__ void reduce_sum_runs_kernel(const float* __restrict__ in, int n, int run, float scale,
+                                       float* __restrict__ out) {
+  __shared__ float scratch[4];
+  const float s = block_sum_256(strided_sum_256_runs(in, n, run, threadIdx.x), scratch);
+  if (threadIdx.x == 0) out[0] = s * scale;
+}
+
 }  // namespace rg
 
 namespace rg {
@@ -784,6 +744,12 @@ int rg_bcq_filter(const float* imitator_logits, int batch, int num_actions, doub
 int rg_reduce_sum(const float* in, int n, float scale, float* out, rg_stream_t stream) {
   if (!in || !out || n < 0) return RG_EINVAL;
   RG_LAUNCH(reduce_sum_kernel, dim3(1), dim3(HEAD_THREADS), (hipStream_t)stream, in, n, scale, out);
+  return (int)hipGetLastError();
+}
+
+int rg_reduce_sum_runs(const float* in, int n, int run, float scale, float* out, rg_stream_t stream) {
+  if (!in || !out || n < 0 || run < 1) return RG_EINVAL;
+  RG_LAUNCH(reduce_sum_runs_kernel, dim3(1), dim3(HEAD_THREADS), (hipStream_t)stream, in, n, run, scale, out);
   return (int)hipGetLastError();
 }
 

@@ -21,6 +21,7 @@
 
 #include "rg_mlp_frag.h"
 #include "rg_reduce.h"
+#include "rg_dqn_head_row.h"
 #include <cstdio>
 
 namespace rg {
@@ -96,12 +97,20 @@ __device__ __forceinline__ void grouped_whole_tile_out(bf16_t* act, int pitch, i
 // tile assignment loses the dispatcher's load balancing; the kernel stays one tile per workgroup.)
 // GROUPED: the launch of a stack whose output layer takes per-tile weights (rg_mlp_desc.tile_key, qr_grouped.hip) is its
 // own instantiation — the ordinary kernel does not carry its code paths (or their registers).
-template <int TN, int NW, int PITCH, bool GROUPED>
-__device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
+// PAIR: one pass of the paired online forward (mlp_fwd_pair_kernel, below): the same workgroup runs this body twice over the
+// same LDS tile — `pass` 0 / 1, `on_state` = this pass reads `state` and saves, else `next_state` — with the thin output
+// layer's weights copied to LDS in pass 0 only, the first pass's Q rows parked behind them, and the TD head
+// (rg_dqn_head_row.h) in the row-store pass of the second output layer.
+template <int TN, int NW, int PITCH, bool GROUPED, bool PAIR = false>
+__device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a, const PairArgs* pp = nullptr, int pass = 0, bool on_state = false) {
   constexpr int THREADS = MlpCfg<NW>::THREADS, RING = MlpCfg<NW>::RING;
+  static_assert(!PAIR || (!GROUPED && NW == 8), "the pair is the plain 8-wave kernel");
+  const int save = PAIR ? (on_state ? 1 : 0) : a.save;
   RG_DYN_LDS(smem);
   bf16_t* act = (bf16_t*)smem;
-  const int tid = threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
+  // (PAIR: an opaque copy per pass — what the two copies of the body derive from the lane is the same, and shared between
+  // them those addresses would sit in registers across the hidden layers' main loops)
+  const int tid = PAIR ? opaque((int)threadIdx.x) : (int)threadIdx.x, lane = tid & 63, wave = wave_uniform(tid >> 6);
   const int lr = lane & 31, lg = lane >> 5;
   const int tile = GROUPED ? grouped_tile(blockIdx.x, (a.batch + FB_BM - 1) / FB_BM) : (int)blockIdx.x;
   if (GROUPED && tile * FB_BM >= round_up(a.batch, FB_BM)) return;  // padding blocks (workgroup-uniform)
@@ -109,7 +118,15 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
   constexpr int pitch = PITCH;
   const int k0p = round_up(a.dims[0], 32);
   RG_STAMP(0);
-  if (a.rowmap) {  // grouped space: rows gathered through the map
+  if constexpr (PAIR) {
+    const PairIO& io = pp->io[on_state ? 1 : 0];
+    const void* x = io.x;
+    const long ldx = io.ldx;
+    if (io.x_is_f32)
+      load_tile_to_lds<float, THREADS>(act, pitch, (const float*)x, ldx, row_base, a.batch, a.dims[0], k0p, tid);
+    else
+      load_tile_to_lds<bf16_t, THREADS>(act, pitch, (const bf16_t*)x, ldx, row_base, a.batch, a.dims[0], k0p, tid);
+  } else if (a.rowmap) {  // grouped space: rows gathered through the map
     if (a.x_is_f32)
       load_tile_rows_mapped<float, THREADS>(act, pitch, (const float*)a.x, a.ldx, a.rowmap, row_base, a.dims[0], k0p, tid);
     else
@@ -130,11 +147,11 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
     load_tile_to_lds<bf16_t, THREADS>(act, pitch, (const bf16_t*)a.x, a.ldx, row_base, a.batch, a.dims[0], k0p, tid);
   __syncthreads();
   RG_STAMP(1);
-  if (a.save == 1 && a.act_frag[0]) emit_frags_from_lds(act, pitch, k0p / 32, a.act_frag[0], tile * 4, wave, NW, lane);
+  if (save == 1 && a.act_frag[0]) emit_frags_from_lds(act, pitch, k0p / 32, a.act_frag[0], tile * 4, wave, NW, lane);
   // a thin output layer's weights travel to LDS while the hidden layers compute (rg_mlp_frag.h: out_lds_prefetch)
-  const bool out_lds = !GROUPED && a.out_lds;
+  const bool out_lds = PAIR || (!GROUPED && a.out_lds);
   char* wo = (char*)(act + FB_BM * pitch);
-  if (out_lds) out_lds_prefetch(a.wfrag[a.n_layers - 1], (a.dims[a.n_layers - 1] + 15) / 16, wo, wave, NW, lane);
+  if (out_lds && pass == 0) out_lds_prefetch(a.wfrag[a.n_layers - 1], (a.dims[a.n_layers - 1] + 15) / 16, wo, wave, NW, lane);
 
   for (int l = 0; l < a.n_layers; ++l) {
     const int K = a.dims[l], N = a.dims[l + 1];
@@ -152,9 +169,15 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
                               k_rotation(blockIdx.x, wave, KC), wave / (NW / 2));
       RG_STAMP(2 + 4 * l);
       unsigned PK[4][TN][8];
-      unsigned* sign_dst = a.save ? a.act_sign[l + 1] : nullptr;  // plane base; the lane offset is applied at the store
-      RG_DISPATCH_ACT(a.acts[l], (fwd_hidden_pack<TN, A_>(acc, a.bias[l], fwd_save_dst(a, l),
-                                                          sign_dst, N / 32, tile * 4, wave, lane, PK)));
+      unsigned* sign_dst = save ? a.act_sign[l + 1] : nullptr;  // plane base; the lane offset is applied at the store
+      if constexpr (PAIR) {
+        // ReLU hidden layers only (the launch checks): the pair carries two copies of this epilogue, and one per activation
+        // kind on top of that puts the kernel's branches out of short range (a scratch slot for the long jumps)
+        fwd_hidden_pack<TN, ACT_RELU>(acc, a.bias[l], save ? a.act_frag[l + 1] : nullptr, sign_dst, N / 32, tile * 4, wave, lane, PK);
+      } else {
+        RG_DISPATCH_ACT(a.acts[l], (fwd_hidden_pack<TN, A_>(acc, a.bias[l], fwd_save_dst(a, l),
+                                                            sign_dst, N / 32, tile * 4, wave, lane, PK)));
+      }
       RG_STAMP(3 + 4 * l);
       __syncthreads();  // every wave is done reading the layer input
       RG_STAMP(4 + 4 * l);
@@ -211,7 +234,27 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
         // row tiles with a ring of 8 / 16 chunks — was measured on the C3 grouped forward in rounds 2 and 3: 171 us against
         // 169 us for this loop, C3 step 1.119 / 1.121 against 1.101 ms; its burst of output stores at the end costs more than
         // the re-read fragments.  Ablations of the 189 us target forward: head MFMAs removed -43 us, output stores -20..-28.)
-        if (!GROUPED && NTo == 1 && NW == 8 && KC >= 8) {
+        // PAIR: what the head needs of this thread's row (the row-store pass below: 4 lanes per row, dqn_head_lanes_kernel<4>'s
+        // mapping) is requested HERE, before the output layer's K loop, like b_tile0 — the hidden layers' accumulators are dead
+        f32x4 h_m4, h_qt4, h_ac4;
+        float h_rew = 0.f, h_nt = 0.f, h_ge = 0.f;
+        int h_b = 0;
+        bool h_live = false;
+        if constexpr (PAIR) {
+          if (pass == 1) {
+            const int it = wave * 64 + opaque(lane), row = row_base + (it >> 2);
+            h_live = row < a.batch;
+            h_b = h_live ? row : a.batch - 1;  // rows past the end: the last row's operands, nothing stored
+            const long o = (long)h_b * 16 + (it & 3) * 4;
+            h_m4 = *(const f32x4*)(pp->next_mask + o);
+            h_qt4 = *(const f32x4*)(pp->qn_target + o);
+            h_ac4 = *(const f32x4*)(pp->action + o);
+            h_rew = pp->reward[h_b];
+            h_nt = pp->not_terminal[h_b];
+            if (pp->gamma_exponent) h_ge = pp->gamma_exponent[h_b];
+          }
+        }
+        if (PAIR || (!GROUPED && NTo == 1 && NW == 8 && KC >= 8)) {
           // one column tile (<= 32 outputs, e.g. 16 Q-values): four 32x32 tiles for eight waves.  The loop is a chain
           // of L2 round trips (7 % of a workgroup's life with four waves idle), so two waves share a tile, each
           // summing half of K; the upper four hand their accumulators over through the activation tile, dead by then.
@@ -233,7 +276,7 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
           // and a full tile — the tile's 128 x N block as ONE contiguous run, whatever N is
           const bool aligned16 = (reinterpret_cast<uintptr_t>(a.out32) & 15) == 0;
           const bool dense_run = a.ldo == N && row_base + FB_BM <= a.batch;
-          const bool rowstore = !a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0));
+          const bool rowstore = PAIR || (!a.out_scatter && aligned16 && (dense_run || ((N & 3) == 0 && (a.ldo & 3) == 0)));
           if (rowstore) {  // (workgroup-uniform)
             float* outs = (float*)act + half * (FB_BM * 32);
             float* bias_s = (float*)act + 2 * (FB_BM * 32);  // the bias (requested before the K loop) travels through LDS too
@@ -247,7 +290,31 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
             RG_STAMP(19);
             const float* lo_ = (const float*)act;
             const float* hi_ = lo_ + FB_BM * 32;
-            if (dense_run) {
+            if constexpr (PAIR) {  // N == 16 (the launch checks): thread it = row it / 4, float4 it % 4 of the tile's Q block
+              const int it = wave * 64 + o_ln, rel = it >> 2, c4 = it & 3, row = row_base + rel;
+              const f32x4 l4 = *(const f32x4*)(lo_ + it * 4), h4 = *(const f32x4*)(hi_ + it * 4);
+              const f32x4 b4 = *(const f32x4*)(bias_s + c4 * 4);
+              float o[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) o[e] = (l4[e] + h4[e]) + b4[e];
+              act_apply_n(o, out_act);
+              const f32x4 mine = f32x4{o[0], o[1], o[2], o[3]};
+              if (row < a.batch) *(f32x4*)(pp->io[on_state ? 1 : 0].out + (long)row * 16 + c4 * 4) = mine;
+              // the first pass's Q rows wait behind the output layer's weights (8 KB; read back by the thread that wrote them)
+              f32x4* park = (f32x4*)(wo + (size_t)KC * 512);
+              if (pass == 0) {
+                park[it] = mine;
+              } else {
+                const f32x4 other = park[it];
+                const f32x4 q4 = on_state ? mine : other, qon4 = on_state ? other : mine;
+                const float loss = dqn_head_lanes_row<4>(h_m4, h_qt4, pp->double_q ? qon4 : h_qt4, h_ac4, q4, c4, h_b, h_live, h_rew,
+                                                         pp->reward_boosts, h_nt, pp->gamma, pp->gamma_exponent != nullptr, h_ge,
+                                                         a.batch, pp->double_q, pp->loss_type, pp->dq, pp->next_q, pp->next_idx,
+                                                         pp->q_sel);
+                const float ws = dqn_head_wave_sum(loss);  // 16 rows: one of the 16 wave sums dqn_head_lanes_kernel<4> adds per partial
+                if (o_ln == 0) pp->wave_sums[tile * NW + wave] = ws;
+              }
+            } else if (dense_run) {
               float* dst = a.out32 + (long)row_base * N;
               for (int it = wave * 64 + o_ln; it < (FB_BM * N) >> 2; it += THREADS) {
                 const f32x4 l4 = *(const f32x4*)(lo_ + it * 4), h4 = *(const f32x4*)(hi_ + it * 4);
@@ -259,7 +326,7 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
               }
             }
             const int np = N >> 2;  // 16-byte pieces per row
-            for (int it = wave * 64 + o_ln; !dense_run && it < FB_BM * np; it += THREADS) {  // (tid, rebuilt from the live lane: tid itself is dead by now)
+            for (int it = wave * 64 + o_ln; !PAIR && !dense_run && it < FB_BM * np; it += THREADS) {  // (tid, rebuilt from the live lane: tid itself is dead by now)
               const int rel = it / np, c4 = it - rel * np;
               const int row = row_base + rel;
               if (row < a.batch) {
@@ -352,6 +419,24 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a) {
       RG_STAMP(2 + 4 * l);
     }
   }
+}
+
+// The online network's two forwards of a DQN step in one workgroup per 128-row tile: next_state (not saving) and state
+// (saving), then the TD head for those rows (rg_dqn_online_pair_forward).  Half of the workgroups run (next_state, state),
+// the other half (state, next_state): identical workgroups that start together stay in lockstep, and every CU storing its
+// 128 KB of fragment records at the same moment is what the saving forward's PACK phases wait for
+// (profiles/NOTES_r07.md); with the orders mixed about half of the CUs are in a saving pass at any moment.
+#ifndef RG_PAIR_ORDER_SHIFT
+#define RG_PAIR_ORDER_SHIFT 0  // which workgroups take which order: bit RG_PAIR_ORDER_SHIFT of the index (3: every XCD has both)
+#endif
+template <int TN, int NW, int PITCH>
+__global__ void RG_LAUNCH_BOUNDS(NW * 64, 1) mlp_fwd_pair_kernel(MlpArgs a, PairArgs p) {
+  const bool state_first = (((int)blockIdx.x >> RG_PAIR_ORDER_SHIFT) & 1) != 0;  // (workgroup-uniform)
+  // (two copies of the body, not a loop over the pass: in a loop the launch arguments both passes read are hoisted above it
+  // and the scalar registers that hold them spill into vector registers the 512-wide kernel does not have)
+  mlp_fwd_fused_body<TN, NW, PITCH, false, true>(a, &p, 0, state_first);
+  __syncthreads();  // the row-store pass reads the (dead) activation tile the next pass loads its input into
+  mlp_fwd_fused_body<TN, NW, PITCH, false, true>(a, &p, 1, !state_first);
 }
 
 template <int TN, int NW, int PITCH>
@@ -1203,6 +1288,7 @@ struct ReduceTailArgs {
   int elem_blocks;
   const float* sum_in;
   int sum_n;
+  int sum_run;  // > 1: sum_in holds per-wave sums, runs of sum_run of them are added in order first (rg_reduce.h: strided_sum_256_runs)
   float sum_scale;
   float* sum_out;
 };
@@ -1224,7 +1310,8 @@ __global__ void reduce_tail_kernel(ReduceTailArgs T) {
   }
   // reduce_sum_kernel (heads.hip): strided partial sums, block_sum_256's fixed order
   __shared__ float scratch[4];
-  float acc = strided_sum_256(T.sum_in, T.sum_n, threadIdx.x);
+  float acc = T.sum_run > 1 ? strided_sum_256_runs(T.sum_in, T.sum_n, T.sum_run, threadIdx.x)
+                            : strided_sum_256(T.sum_in, T.sum_n, threadIdx.x);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) acc += shfl_xor(acc, off);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = acc;
@@ -1515,20 +1602,21 @@ __global__ void mlp_update_tiles_kernel(UpdateTileArgs T) {
 }
 
 // the three (hidden width, pitch) instantiations of a fused kernel template
-#define RG_LAUNCH_FUSED(KERNEL, hidden, pitch, grid, lds, stream, args)                                      \
+#define RG_LAUNCH_FUSED_ARGS(KERNEL, hidden, pitch, grid, lds, stream, ...)                                     \
   do {                                                                                                       \
     const dim3 block_(FB_NW * 64);                                                                           \
     if ((hidden) == 256 && (pitch) == 264) {                                                                 \
       RG_ALLOW_LDS((KERNEL<256 / (32 * FB_NW), FB_NW, 264>), lds);                                           \
-      RG_LAUNCH_DYN((KERNEL<256 / (32 * FB_NW), FB_NW, 264>), grid, block_, lds, (hipStream_t)stream, args); \
+      RG_LAUNCH_DYN((KERNEL<256 / (32 * FB_NW), FB_NW, 264>), grid, block_, lds, (hipStream_t)stream, __VA_ARGS__); \
     } else if ((hidden) == 256) {                                                                            \
       RG_ALLOW_LDS((KERNEL<256 / (32 * FB_NW), FB_NW, 520>), lds);                                           \
-      RG_LAUNCH_DYN((KERNEL<256 / (32 * FB_NW), FB_NW, 520>), grid, block_, lds, (hipStream_t)stream, args); \
+      RG_LAUNCH_DYN((KERNEL<256 / (32 * FB_NW), FB_NW, 520>), grid, block_, lds, (hipStream_t)stream, __VA_ARGS__); \
     } else {                                                                                                 \
       RG_ALLOW_LDS((KERNEL<512 / (32 * FB_NW), FB_NW, 520>), lds);                                           \
-      RG_LAUNCH_DYN((KERNEL<512 / (32 * FB_NW), FB_NW, 520>), grid, block_, lds, (hipStream_t)stream, args); \
+      RG_LAUNCH_DYN((KERNEL<512 / (32 * FB_NW), FB_NW, 520>), grid, block_, lds, (hipStream_t)stream, __VA_ARGS__); \
     }                                                                                                        \
   } while (0)
+#define RG_LAUNCH_FUSED(KERNEL, hidden, pitch, grid, lds, stream, args) RG_LAUNCH_FUSED_ARGS(KERNEL, hidden, pitch, grid, lds, stream, args)
 
 }  // namespace rg
 
@@ -1608,6 +1696,49 @@ int rg_mlp_forward_fused(const rg_mlp_desc* d, const void* x, int x_dtype, int64
   }
   if (d->tile_key) RG_LAUNCH_FUSED(mlp_fwd_grouped_kernel, d->dims[1], a.pitch, grid, lds, stream, a);
   else RG_LAUNCH_FUSED(mlp_fwd_fused_kernel, d->dims[1], a.pitch, grid, lds, stream, a);
+  return (int)hipGetLastError();
+}
+
+int rg_dqn_pair_wave_sums(int batch) { return (batch + FB_BM - 1) / FB_BM * FB_NW; }
+
+int rg_dqn_online_pair_forward(const rg_mlp_desc* d, const void* state, int state_dtype, int64_t ld_state,
+                               const void* next_state, int next_state_dtype, int64_t ld_next_state, int batch, float* q,
+                               float* qn_online, const float* qn_target, const float* action, const float* next_mask,
+                               const float* reward, const float* reward_boosts, const float* not_terminal, double gamma,
+                               const float* gamma_exponent, int double_q, int loss_type, float* dq, float* loss_wave_sums,
+                               float* next_q, int64_t* next_idx, float* q_sel, rg_stream_t stream) {
+  if (!fused_supported(d)) return RG_EUNSUPPORTED;
+  if (!state || !next_state || !q || !qn_online || !qn_target || !action || !next_mask || !reward || !not_terminal || !dq ||
+      !loss_wave_sums || batch <= 0)
+    return RG_EINVAL;
+  if (loss_type != RG_LOSS_MSE && loss_type != RG_LOSS_HUBER) return RG_EINVAL;
+  // the plain shape only: bf16 operands, one input panel in batch order, a plain 16-wide output layer whose weights fit
+  // behind the activation tile (rg_mlp_forward_fused's out_lds condition) with the parked Q rows next to them
+  const int L = d->n_layers, KCo = (d->dims[L - 1] + 15) / 16;
+  if (d->x3 || d->x2 || d->rowmap || d->tile_key || L < 2 || d->dims[L] != 16 || KCo < 8 || (KCo & 1)) return RG_EUNSUPPORTED;
+  for (int l = 0; l + 1 < L; ++l)
+    if (d->acts[l] != RG_ACT_RELU) return RG_EUNSUPPORTED;
+  if (((uintptr_t)q | (uintptr_t)qn_online | (uintptr_t)qn_target | (uintptr_t)action | (uintptr_t)next_mask | (uintptr_t)dq) & 15)
+    return RG_EUNSUPPORTED;
+  MlpArgs a;
+  int rc = fill_args(d, batch, a, 0);
+  if (rc) return rc;
+  for (int l = 0; l < L; ++l)
+    if (!d->act_frag[l]) return RG_EINVAL;  // the state pass saves as rg_mlp_forward_fused(save = 1)
+  const size_t park = (size_t)FB_BM * 16 * sizeof(float);
+  const size_t lds = (size_t)FB_BM * a.pitch * sizeof(bf16_t) + (size_t)KCo * 512 + park;
+  if (lds > 160 * 1024) return RG_EUNSUPPORTED;
+  a.x = nullptr; a.ldx = 0; a.x_is_f32 = 0; a.out32 = nullptr; a.ldo = 16; a.save = 0;
+  a.stage_out = 0; a.out_lds = 1;
+  PairArgs p;
+  p.io[0] = PairIO{next_state, (long)ld_next_state, qn_online, next_state_dtype == RG_DT_F32, 0};
+  p.io[1] = PairIO{state, (long)ld_state, q, state_dtype == RG_DT_F32, 0};
+  p.qn_target = qn_target; p.action = action; p.next_mask = next_mask; p.reward = reward;
+  p.reward_boosts = reward_boosts; p.not_terminal = not_terminal; p.gamma_exponent = gamma_exponent; p.gamma = (float)gamma;
+  p.double_q = double_q; p.loss_type = loss_type; p.dq = dq; p.wave_sums = loss_wave_sums; p.next_q = next_q;
+  p.next_idx = next_idx; p.q_sel = q_sel;
+  const dim3 grid((batch + FB_BM - 1) / FB_BM);
+  RG_LAUNCH_FUSED_ARGS(mlp_fwd_pair_kernel, d->dims[1], a.pitch, grid, lds, stream, a, p);
   return (int)hipGetLastError();
 }
 
@@ -2053,7 +2184,7 @@ int rg_mlp_wgrad_fused(const rg_mlp_desc* d, int batch, void* workspace, size_t 
   for (int i = C.n; i <= FB_MAXL; ++i) C.block_begin[i] = blocks;
   for (int i = C.n; i < FB_MAXL; ++i) { C.partials[i] = nullptr; C.out[i] = nullptr; C.N[i] = 0; }
   if (d->sum_in && (!d->sum_out || d->sum_n <= 0)) return RG_EINVAL;
-  T.sum_in = d->sum_in; T.sum_n = d->sum_n; T.sum_scale = (float)d->sum_scale; T.sum_out = d->sum_out;
+  T.sum_in = d->sum_in; T.sum_n = d->sum_n; T.sum_run = d->sum_run; T.sum_scale = (float)d->sum_scale; T.sum_out = d->sum_out;
   RG_LAUNCH(reduce_tail_kernel, dim3((unsigned)(elem_blocks + blocks + (d->sum_in ? 1 : 0))), dim3(256), (hipStream_t)stream, T);
   return (int)hipGetLastError();
 }

@@ -86,6 +86,26 @@ struct MlpArgs {
   long dz_lo[FB_MAXL];
 };
 
+// what the paired online forward (mlp_fused.hip: mlp_fwd_pair_kernel) takes beside the stack's MlpArgs: its two inputs and
+// outputs, and the TD head's operands (rg_dqn_head's, [B, 16] matrices contiguous)
+struct PairIO {
+  const void* x;  // [batch, dims[0]] row-major, bf16 or fp32
+  long ldx;
+  float* out;     // [batch, 16] fp32 = network(x)
+  int x_is_f32, pad_;
+};
+struct PairArgs {
+  PairIO io[2];  // [0] = next_state -> qn_online (not saving), [1] = state -> q (saving); indexed, not selected: one scalar load
+  const float *qn_target, *action, *next_mask, *reward, *reward_boosts, *not_terminal, *gamma_exponent;
+  float gamma;
+  int double_q, loss_type;
+  float* dq;
+  float* wave_sums;  // [tiles * 8]: the loss terms of 16 rows each, summed in dqn_head_lanes_kernel<4>'s lane order
+  float* next_q;
+  int64_t* next_idx;
+  float* q_sel;
+};
+
 __device__ __forceinline__ int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
 // compile-time activation (a runtime `switch` per element would bloat the unrolled epilogues until

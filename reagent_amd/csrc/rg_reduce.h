@@ -34,4 +34,30 @@ __device__ __forceinline__ float strided_sum_256(const float* __restrict__ in, i
          (((a[8] + a[9]) + (a[10] + a[11])) + ((a[12] + a[13]) + (a[14] + a[15])));
 }
 
+// The same sum over values that are themselves ordered sums of runs: value i = 0 + in[i * run] + in[i * run + 1] + ...
+// (`run` terms, those past n_in counting as 0) — the per-wave loss sums of the paired online forward (mlp_fused.hip), whose
+// runs of 16 are what dqn_head_lanes_kernel<4> adds, in this order, into one partial per 256 rows.
+__device__ __forceinline__ float run_sum(const float* __restrict__ in, int n_in, int run, int i) {
+  float s = 0.f;
+  for (int w = 0; w < run; ++w) {
+    const long j = (long)i * run + w;
+    s += j < n_in ? in[j] : 0.f;
+  }
+  return s;
+}
+__device__ __forceinline__ float strided_sum_256_runs(const float* __restrict__ in, int n_in, int run, int tid) {
+  const int n = (n_in + run - 1) / run;
+  float a[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) a[j] = 0.f;
+  int i = tid;
+  for (; i + 15 * 256 < n; i += 16 * 256) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) a[j] += run_sum(in, n_in, run, i + j * 256);
+  }
+  for (; i < n; i += 256) a[0] += run_sum(in, n_in, run, i);
+  return (((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]))) +
+         (((a[8] + a[9]) + (a[10] + a[11])) + ((a[12] + a[13]) + (a[14] + a[15])));
+}
+
 }  // namespace rg

@@ -432,7 +432,7 @@ class FusedMLP:
         d.x3 = int(self.x3)
         d.dx_col0 = 0
         d.dx_only = 0
-        d.defer_db, d.sum_n = 0, 0
+        d.defer_db, d.sum_n, d.sum_run = 0, 0, 0
         d.db_partials, d.sum_in, d.sum_out = None, None, None
         for i, v in enumerate(self.dims):
             d.dims[i] = v
@@ -481,12 +481,51 @@ class FusedMLP:
         self._saved = save
         return out32
 
+    def dqn_pair_supported(self, num_actions: int) -> bool:
+        """the shape rg_dqn_online_pair_forward serves: a bf16 stack of ReLU hidden layers with a 16-wide output whose
+        weights fit in LDS"""
+        k = self.dims[-2]
+        return (not self.x3 and num_actions == 16 and self.dims[-1] == 16 and k >= 128 and ((k + 15) // 16) % 2 == 0
+                and all(a == L.ACT["relu"] for a in self.acts[:-1]))
+
+    def dqn_pair_forward(self, state: torch.Tensor, next_state: torch.Tensor, q, qn_online, qn_target, action, next_mask, reward,
+                         reward_boosts, not_terminal, gamma, gamma_exponent, double_q, loss_type, dq, wave_sums,
+                         next_q=None, next_idx=None, q_sel=None):
+        """forward(next_state, qn_online, save=False) + forward(state, q, save=True) + ops.dqn_head in ONE launch, bit for
+        bit (rg_dqn_online_pair_forward); qn_target must have been computed.  The loss leaves as wave_sums
+        [ops.dqn_pair_wave_sums(B)]: finished by backward(tail_sum=(wave_sums, 1 / B, out, ops.DQN_PAIR_RUN)) or
+        ops.reduce_sum_runs."""
+        B, A = q.shape
+        ops._chk_dev(state, next_state, q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal,
+                     gamma_exponent, dq, wave_sums, next_q, next_idx, q_sel)
+        assert state.shape == (B, self.dims[0]) and next_state.shape == (B, self.dims[0])
+        assert state.stride(1) == 1 and next_state.stride(1) == 1
+        for t in (q, qn_online, qn_target, action, next_mask, dq):
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.shape == (B, A)
+        for t in (reward, not_terminal, gamma_exponent):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and t.numel() == B)
+        assert reward_boosts is None or (reward_boosts.dtype == torch.float32 and reward_boosts.numel() == A)
+        assert wave_sums.dtype == torch.float32 and wave_sums.numel() == ops.dqn_pair_wave_sums(B)
+        self._ensure_ws(B, state.device, training=True)
+        d = self._fill_desc()
+        d.x2, d.ldx2, d.x_split, d.rowmap = None, 0, 0, None
+        # (recorded as the forward entry point with the rows it covers: both passes' FLOP are counted as a forward's)
+        ops._run("rg_mlp_forward_fused", dict(B=2 * B, save=1, dims=tuple(self.dims), pair=1),
+                 lambda: L.lib().rg_dqn_online_pair_forward(
+                     d, state.data_ptr(), ops.dt_code(state.dtype), state.stride(0), next_state.data_ptr(),
+                     ops.dt_code(next_state.dtype), next_state.stride(0), B, L.ptr(q), L.ptr(qn_online), L.ptr(qn_target),
+                     L.ptr(action), L.ptr(next_mask), L.ptr(reward), L.ptr(reward_boosts), L.ptr(not_terminal), float(gamma),
+                     L.ptr(gamma_exponent), int(double_q), loss_type, L.ptr(dq), L.ptr(wave_sums), L.ptr(next_q),
+                     L.ptr(next_idx), L.ptr(q_sel), L.stream_ptr()))
+        self._saved = 1
+
     def backward(self, dout32: torch.Tensor, xt, dw: List[torch.Tensor], db: List[torch.Tensor],
                  dx32: Optional[torch.Tensor] = None, skip_wgrad: bool = False,
                  out32: Optional[torch.Tensor] = None, dx_col0: int = 0, tail_sum=None):
         """dx_col0: dx32 receives the gradient of input columns [dx_col0, in_features) only (a multiple of 32).
         tail_sum = (partials fp32 [n], scale, out fp32 [1]): out = scale * sum(partials) is evaluated in the weight
-        gradient's reduce launch (the mean loss of the step from the loss head's partials: one launch fewer)."""
+        gradient's reduce launch (the mean loss of the step from the loss head's partials: one launch fewer).  A fourth
+        element `run` > 1: the partials are per-wave sums whose runs of `run` are added in order first (dqn_pair_forward)."""
         dout32 = _through_output_activation(self.acts[-1], dout32, out32)
         B = dout32.shape[0]
         assert self._ws.get("key") == (B, dout32.device, True), "backward needs a saving forward first"
@@ -521,15 +560,16 @@ class FusedMLP:
             if defer:
                 d.db_partials = ws["bwd"].data_ptr()
             if tail_sum is not None:
-                part, scale, out = tail_sum
+                part, scale, out = tail_sum[:3]
                 L.require_cuda(part)
                 L.require_cuda(out)
                 assert part.dtype == torch.float32 and part.is_contiguous() and out.dtype == torch.float32
                 d.sum_in, d.sum_n, d.sum_scale, d.sum_out = part.data_ptr(), part.numel(), float(scale), out.data_ptr()
+                d.sum_run = int(tail_sum[3]) if len(tail_sum) > 3 else 0
             wsb = ws["wgrad"].numel() * 4
             ops._run("rg_mlp_wgrad_fused", dict(B=B, dims=tuple(self.dims)),
                      lambda: lib.rg_mlp_wgrad_fused(d, B, ws["wgrad"].data_ptr(), wsb, L.stream_ptr()))
-            d.db_partials, d.sum_in, d.sum_out, d.sum_n = None, None, None, 0
+            d.db_partials, d.sum_in, d.sum_out, d.sum_n, d.sum_run = None, None, None, 0, 0
         else:
             assert tail_sum is None, "tail_sum rides in the weight gradient's launch"
 

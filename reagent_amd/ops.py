@@ -481,6 +481,13 @@ def dqn_head_partials(batch: int) -> int:
     return int(L.lib().rg_dqn_head_partials(batch))
 
 
+def dqn_pair_wave_sums(batch: int) -> int:
+    return int(L.lib().rg_dqn_pair_wave_sums(batch))
+
+
+DQN_PAIR_RUN = 16  # wave sums per loss partial of dqn_head (256 rows, 16 rows per wave at 16 actions)
+
+
 def dqn_head(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal, gamma,
              gamma_exponent, double_q, loss_type, dq, loss_partials, next_q=None, next_idx=None,
              q_sel=None):
@@ -578,6 +585,14 @@ def qr_head(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, n
                                     L.ptr(reward), L.ptr(reward_boosts), L.ptr(not_terminal), float(gamma),
                                     L.ptr(gamma_exponent), L.ptr(quantiles), batch, A, num_atoms, int(maxq),
                                     L.ptr(dq), L.ptr(loss_partials), L.ptr(all_q), L.stream_ptr()))
+
+
+def reduce_sum_runs(inp, n: int, run: int, scale: float, out):
+    """out = scale * sum of the n inputs, each run of `run` of them added in order first (the per-wave loss sums of
+    FusedMLP.dqn_pair_forward with run = 16: the bits of dqn_head's partials through reduce_sum)"""
+    _chk_dev(inp, out)
+    _run("rg_reduce_sum_runs", dict(n=n, run=run),
+         lambda: L.lib().rg_reduce_sum_runs(L.ptr(inp), n, run, scale, L.ptr(out), L.stream_ptr()))
 
 
 def reduce_sum(inp, n: int, scale: float, out):

@@ -9,6 +9,8 @@ One training step (reference :241-304, algorithmic form of SURVEY.md §8d: 3 for
     grads     = backward                         rg_fc_wgrad / rg_fc_dgrad x L
     Adam, soft update                            rg_adam_step, rg_soft_update (via the optimizers)
 The CPE-only 4th forward of the reference (:268) is dead when CPE is off and is not executed.
+The native step on the plain shape (fused bf16 stacks, 16 actions: DQNTrainer._pair_wanted) runs q'_online, q and the TD head
+as ONE launch after q'_target (rg_dqn_online_pair_forward), bit-identical to the sequence above.
 """
 import logging
 from dataclasses import dataclass, field
@@ -405,10 +407,13 @@ class QStepCore(DQNTrainerBaseLightning):
         ts.stage_weights(need_transposed=False)
         xs, self._xs_t = qs.stage_input(state, need_transposed=True)
         xn, _ = qs.stage_input(next_state, need_transposed=False)
-        if self._needs_online_next():
+        # the plain native DQN step: the target forward, then the online network's two forwards and the TD head in one launch
+        paired = self._pair_wanted(qs, ts)
+        if not paired and self._needs_online_next():
             qs.forward(xn, self._qn_online, save=False)
         ts.forward(xn, self._qn_target, save=False)
-        qs.forward(xs, self._q, save=True)
+        if not paired:
+            qs.forward(xs, self._q, save=True)
         gamma_exp = None
         if self.use_seq_num_diff_as_time_diff:
             assert self.multi_steps is None
@@ -423,8 +428,14 @@ class QStepCore(DQNTrainerBaseLightning):
                 next_mask = self._bcq_mask(next_mask, next_state)
         else:  # SARSA: the taken next action is the only "possible" one (dqn_trainer.py:218-224)
             next_mask = self._f32c(b.next_action)
-        self._run_head(b, B, self._f32c(b.action), next_mask, boosts, gamma_exp)
+        if paired:
+            self._run_pair(b, B, xs, xn, self._f32c(b.action), next_mask, boosts, gamma_exp)
+        else:
+            self._run_head(b, B, self._f32c(b.action), next_mask, boosts, gamma_exp)
         return self._loss
+
+    def _pair_wanted(self, qs, ts) -> bool:
+        return False
 
     def _hip_backward(self, grad_out=None, async_reduce: bool = False):
         if grad_out is not None:
@@ -770,6 +781,7 @@ class DQNTrainer(QStepCore):
     def _alloc_head(self, batch, device):
         f32 = dict(dtype=torch.float32, device=device)
         self._loss_partials = torch.empty(ops.dqn_head_partials(batch), **f32)
+        self._wave_sums = torch.empty(ops.dqn_pair_wave_sums(batch), **f32)  # the paired launch's loss, per wave (_run_pair)
         self._next_q = torch.empty(batch, **f32)
         self._next_idx = torch.empty(batch, dtype=torch.int64, device=device)
         self._q_sel = torch.empty(batch, **f32)
@@ -785,6 +797,25 @@ class DQNTrainer(QStepCore):
             self._loss_tail = (self._loss_partials, 1.0 / B, self._loss)  # summed in rg_mlp_wgrad_fused's reduce launch
         else:
             ops.reduce_sum(self._loss_partials, self._loss_partials.numel(), 1.0 / B, self._loss)
+        self.all_action_scores = self._q
+
+    def _pair_wanted(self, qs, ts) -> bool:
+        """The native step (the loss is not read before the backward is enqueued) on the plain shape — fused bf16 stacks
+        on both networks, 16 actions, ReLU hidden layers, no BCQ mask, no batch-norm, no CPE heads — runs
+        FusedMLP.dqn_pair_forward; everything else keeps the three launches + ops.dqn_head."""
+        from ..engine import FusedMLP
+
+        return (self._loss_tail_wanted and type(self)._run_head is DQNTrainer._run_head and isinstance(qs, FusedMLP) and isinstance(ts, FusedMLP)
+                and not ts.x3 and qs.dqn_pair_supported(self.num_actions) and not self.bcq
+                and getattr(self, "_cpe", None) is None and not self._q_has_batch_norm())
+
+    def _run_pair(self, b, B, xs, xn, action, next_mask, boosts, gamma_exp):
+        self._qs.dqn_pair_forward(xs, xn, self._q, self._qn_online, self._qn_target, action, next_mask,
+                                  self._f32c(b.reward).reshape(-1), boosts, self._f32c(b.not_terminal).reshape(-1),
+                                  self.gamma, gamma_exp, self.double_q_learning, self._loss_type, self._dq,
+                                  self._wave_sums, self._next_q, self._next_idx, self._q_sel)
+        # the per-wave loss sums are finished in rg_mlp_wgrad_fused's reduce launch (runs of 16 = ops.dqn_head's partials)
+        self._loss_tail = (self._wave_sums, 1.0 / B, self._loss, ops.DQN_PAIR_RUN)
         self.all_action_scores = self._q
 
     # ---- reference surface --------------------------------------------------------------------
