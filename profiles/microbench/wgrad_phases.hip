@@ -19,13 +19,7 @@ __device__ unsigned long long* g_stamps;
       o_[7] = ((unsigned long long)g.N << 32) | (unsigned)g.K;                        \
     }                                                                                 \
   } while (0)
-#include "../../reagent_amd/csrc/mlp_fused.hip"
-// microbench stubs: entry points of the library that live in other translation units and are not exercised here
-namespace rg {
-int x3_forward_launch(const rg_mlp_desc*, MlpArgs&, hipStream_t) { return RG_EINVAL; }
-int x3_backward_launch(const rg_mlp_desc*, MlpArgs&, hipStream_t) { return RG_EINVAL; }
-void grouped_bias_reduce_launch(const float*, const int*, int, int, float*, int, hipStream_t) {}
-}
+#include "../../reagent_amd/csrc/mlp_wgrad.hip"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -37,8 +31,8 @@ int main() {
   for (int i = 0; i < 5; ++i) d.dims[i] = dims[i];
   for (int l = 0; l < 4; ++l) {
     void *af, *dz; float* dw;
-    hipMalloc(&af, rg_frag_elems(B, dims[l]) * 2); hipMemset(af, 0x3c, rg_frag_elems(B, dims[l]) * 2);
-    hipMalloc(&dz, rg_frag_elems(B, dims[l + 1]) * 2); hipMemset(dz, 0x3c, rg_frag_elems(B, dims[l + 1]) * 2);
+    hipMalloc(&af, frag_elems(B, dims[l]) * 2); hipMemset(af, 0x3c, frag_elems(B, dims[l]) * 2);
+    hipMalloc(&dz, frag_elems(B, dims[l + 1]) * 2); hipMemset(dz, 0x3c, frag_elems(B, dims[l + 1]) * 2);
     hipMalloc((void**)&dw, (size_t)dims[l] * dims[l + 1] * 4);
     d.act_frag[l] = af; d.dz_frag[l] = dz; d.dw[l] = dw;
   }

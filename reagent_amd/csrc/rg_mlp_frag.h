@@ -1,6 +1,7 @@
-// rg_mlp_frag.h — what the fused FullyConnected-stack kernels share (mlp_fused.hip: bf16 operands;
-// mlp_fused_x3.hip: split-bf16 "bf16x3" operands): the kernel argument block, the MFMA C-fragment order of
-// saved activations, the LDS tile helpers and the two-phase epilogue pieces.
+// rg_mlp_frag.h — what the fused FullyConnected-stack kernels share (mlp_fused.hip: bf16 forward / backward;
+// mlp_fused_x3.hip: split-bf16 "bf16x3" forward / backward; mlp_wgrad.hip: both stacks' weight gradient; mlp_update.hip:
+// weight staging and the fused update): the kernel argument block, the MFMA C-fragment order of saved activations, the
+// LDS tile helpers and the two-phase epilogue pieces.
 #pragma once
 #include "rg_gemm.h"
 #include "rg_optim.h"
@@ -737,8 +738,6 @@ static inline int fused_pitch(const rg_mlp_desc* d) {
   return m <= 256 ? 264 : 520;
 }
 
-
-
 // fp32 master weights -> B-fragment order for forward (W) and backward (W^T), zero padded
 __device__ __forceinline__ void stage_weight_elem(const float* __restrict__ w, int N, int K, bf16_t* __restrict__ wf,
                                                   bf16_t* __restrict__ wb, long i, int x3 = 0) {
@@ -764,7 +763,6 @@ __device__ __forceinline__ void stage_weight_elem(const float* __restrict__ w, i
     if (x3) wb[tb + i] = f32_to_bf16(v - bf16_to_f32(hi));
   }
 }
-
 
 static inline size_t frag_elems(int rows, int cols) {
   return (size_t)((rows + 127) / 128 * 128) * (size_t)((cols + 31) / 32 * 32);
@@ -816,6 +814,14 @@ static inline int fill_args(const rg_mlp_desc* d, int batch, MlpArgs& a, int bac
   return RG_OK;
 }
 
+constexpr int X3_BM = 64;  // rows per workgroup of the split-bf16 kernels
+
+// workgroups of a backward launch, padded to whole 128-row tiles: the rows of its bias-gradient partials
+static inline int padded_wgs(const rg_mlp_desc* d, int batch) {
+  const int bm = d->x3 ? X3_BM : FB_BM;
+  return (batch + 127) / 128 * (128 / bm);
+}
+
 // db[g * Ng + n] = sum over the segments of group g of db_part[unit + g][n] (qr_grouped.hip; db_part row pitch Ng): the
 // backward kernel's workgroup `unit` (unit_rows rows of the grouped space: 128 for the bf16 kernels, 64 for the split-bf16 ones)
 // writes the column sums of its rows of group g to row unit + g — distinct for distinct segments, contiguous per group
@@ -825,6 +831,5 @@ void grouped_bias_reduce_launch(const float* db_part, const int* row_begin, int 
 // split-bf16 kernels (mlp_fused_x3.hip); `a` filled by fill_args, launch geometry decided there
 int x3_forward_launch(const rg_mlp_desc* d, MlpArgs& a, hipStream_t stream);
 int x3_backward_launch(const rg_mlp_desc* d, MlpArgs& a, hipStream_t stream);
-constexpr int X3_BM = 64;  // rows per workgroup of the split-bf16 kernels
 
 }  // namespace rg

@@ -1,5 +1,5 @@
 // rg_optim.h — the per-element optimizer arithmetic, shared by the stand-alone kernels (optim.hip)
-// and the fused update (mlp_fused.hip) so that both produce the same bits.  Floating-point
+// and the fused update (mlp_update.hip) so that both produce the same bits.  Floating-point
 // contraction is switched off inside: whether `a + b * c` becomes an FMA would otherwise depend on
 // the surrounding code, and the two call sites differed in the last place on the MI355X.
 #pragma once

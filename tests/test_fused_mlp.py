@@ -391,7 +391,7 @@ torch.save([t.cpu() for t in dw + db], {path!r})
 
 @pytest.mark.parametrize("prec", [L.PREC_BF16, L.PREC_BF16X3])
 def test_unevenly_split_weight_gradient_launch(backend, prec, tmp_path):
-    """rg_mlp_wgrad_fused's round-5 launch plan (mlp_fused.hip: "entries"): when the multi-tile layers' workgroups are exactly one
+    """rg_mlp_wgrad_fused's round-5 launch plan (mlp_wgrad.hip: "entries"): when the multi-tile layers' workgroups are exactly one
     round of the chip and only single-tile layers follow, a part of each multi-tile layer's splits is made shorter and the
     rest longer, as two ENTRIES of the launch (the second with mb_base > 0 and its partial slabs after the first's).  The plan
     keys on the CU count, so only C2's full-size stack meets it on the GPU; here RG_WGRAD_TOTAL / RG_WGRAD_THIN make a small
