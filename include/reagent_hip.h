@@ -35,7 +35,11 @@ enum {
   RG_ACT_LINEAR = 0, RG_ACT_RELU = 1, RG_ACT_LEAKY_RELU = 2, RG_ACT_TANH = 3, RG_ACT_SIGMOID = 4,
   RG_ACT_SOFTPLUS = 5 /* reagent/models/fully_connected_network.py:37-44 ACTIVATION_MAP */
 };
-enum { RG_LOSS_MSE = 0, RG_LOSS_HUBER = 1 }; /* reagent/training/dqn_trainer_base.py:146-155 */
+enum {
+  RG_LOSS_MSE = 0, RG_LOSS_HUBER = 1, /* reagent/training/dqn_trainer_base.py:146-155 */
+  RG_LOSS_BCE_LOGITS = 2 /* ABI 13, rg_pdqn_head only: F.binary_cross_entropy_with_logits,
+                          * reagent/training/parametric_dqn_trainer.py:55-61 */
+};
 
 const char* rg_strerror(int code);
 int rg_abi_version(void);
@@ -218,6 +222,14 @@ typedef struct {
    * sum_run of them is first added in order into one value (what rg_dqn_head adds into one partial per 256 rows) and the
    * values are then summed as above: the same adds in the same order as rg_dqn_head's partials.  0 / 1: as before. */
   int32_t sum_run;
+  /* ABI 13 — tiled two-panel forward (forward only): with x2 != NULL and x_tile = M > 1, `batch` counts TILED rows and
+   * batch row r reads columns [0, x_split) from row r / M of x (ceil(batch / M) rows) and the remaining columns from row r
+   * of x2: the network input cat(state.repeat_interleave(M, 0), candidates) of a parametric DQN step
+   * (FeatureData.get_tiled_batch, reagent/core/types.py:349-365, and FullyConnectedCritic's cat, reagent/models/critic.py:79-92,
+   * as reagent/training/parametric_dqn_trainer.py:134-140 evaluates them) without either being written.  Same bits as the
+   * two-panel forward on the materialised tiled state.  0 / 1: as before.  RG_EINVAL without x2; RG_EUNSUPPORTED with
+   * save != 0, rowmap, tile_key or rg_dqn_online_pair_forward. */
+  int32_t x_tile;
 } rg_mlp_desc; /* host struct */
 
 int rg_mlp_fused_supported(const rg_mlp_desc* d);
@@ -574,6 +586,31 @@ int rg_dqn_online_pair_forward(const rg_mlp_desc* d, const void* state, int stat
                                const float* reward, const float* reward_boosts, const float* not_terminal, double gamma,
                                const float* gamma_exponent, int double_q, int loss_type, float* dq, float* loss_wave_sums,
                                float* next_q, int64_t* next_idx, float* q_sel, rg_stream_t stream);
+
+/* ABI 13 — parametric DQN (Q(s, a) over a per-state list of M = max_num_actions candidate actions).
+ * rg_tile_concat: out[r, :x_cols] = x[r / x_tile, :], out[r, x_cols:] = x2[r, :] for r < rows — the critic input
+ * cat(next_state.get_tiled_batch(M), possible_next_actions) (reagent/core/types.py:349-365 repeat_interleave,
+ * reagent/models/critic.py:79-92 cat; parametric_dqn_trainer.py:134-140) for the engines that do not read two panels in
+ * place (x_tile = 1: the plain cat(state, action) of :166).  fp32 row-major with the given pitches; a pure copy, 16-byte
+ * accesses where pitch and base allow. */
+int rg_tile_concat(const float* x, int64_t ldx, const float* x2, int64_t ldx2, int rows, int x_tile, int x_cols, int x2_cols,
+                   float* out, int64_t ldo, rg_stream_t stream);
+/* rg_pdqn_head: get_max_q_values_with_target (reagent/training/dqn_trainer_base.py:33-77), the TD target with its
+ * discount, the loss and d(mean loss)/dq (reagent/training/parametric_dqn_trainer.py:112-171) in one pass over the batch.
+ * q [B] = q_network(state, action).  maxq != 0: qn_online_all (read with double_q only), qn_target_all [B * M] = the two
+ * networks on the tiled next state, next_mask [B, M]; the values are penalised by -1e9 * (1 - mask) in fp32 as the
+ * reference does, the first maximal index wins (double_q: of the online values, the target value at that index is read),
+ * a fully masked row selects index 0 and yields the penalised value.  maxq == 0 (SARSA): qn_target_all [B] is the target
+ * network's value of (next_state, next_action), the others NULL.  reward, not_terminal [B];
+ * discount = gamma, or gamma ** gamma_exponent[b] when gamma_exponent != NULL (time_diff / step), as for rg_dqn_head.
+ * target = reward + (not_terminal * discount) * next_q.  loss_type: RG_LOSS_MSE, RG_LOSS_HUBER, RG_LOSS_BCE_LOGITS.
+ * Outputs: target [B], dq [B], loss_partials [rg_pdqn_head_partials(B)] whose ordered sum / B is the loss
+ * (rg_reduce_sum finishes it), next_q [B], next_idx [B] int64 (nullable). */
+int rg_pdqn_head_partials(int batch);
+int rg_pdqn_head(const float* q, const float* qn_online_all, const float* qn_target_all, const float* next_mask,
+                 const float* reward, const float* not_terminal, double gamma, const float* gamma_exponent, int batch,
+                 int max_num_actions, int maxq, int double_q, int loss_type, float* target, float* dq,
+                 float* loss_partials, float* next_q, int64_t* next_idx, rg_stream_t stream);
 
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)

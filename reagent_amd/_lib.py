@@ -14,11 +14,12 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RG_LIB: another build of the same library (same-box A/B of compile-time kernel variants); default = the in-tree build
 LIB_PATH = os.environ.get("RG_LIB") or os.path.join(_HERE, "lib", "libreagent_hip.so")
 
-ABI_VERSION = 12  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
+ABI_VERSION = 13  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT = {"linear": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}
 LOSS = {"mse": 0, "huber": 1}
+LOSS_BCE_LOGITS = 2  # RG_LOSS_BCE_LOGITS: rg_pdqn_head only (the discrete trainers reject the name through LOSS)
 MAX_GATHER_COLS = 16
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
@@ -95,6 +96,7 @@ class MlpDesc(ctypes.Structure):
         ("sum_out", c_void_p),
         ("sum_scale", ctypes.c_double),
         ("sum_run", ctypes.c_int32),
+        ("x_tile", ctypes.c_int32),  # ABI 13: batch row r reads row r / x_tile of x (tiled two-panel forward)
     ]
 
 
@@ -231,6 +233,9 @@ SIGNATURES = {
     "rg_replay_dqn_batch_pooled": (c_int, [ctypes.POINTER(ReplayView), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                             ctypes.POINTER(DqnBatchOut), c_void_p]),
     "rg_table_check_actions": (c_int, [ctypes.POINTER(DqnTable), c_void_p, c_int, c_void_p, c_void_p]),
+    "rg_tile_concat": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
+    "rg_pdqn_head_partials": (c_int, [c_int]),
+    "rg_pdqn_head": (c_int, [c_void_p] * 6 + [c_d, c_void_p, c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "rg_bcq_filter": (c_int, [c_void_p, c_int, c_int, c_d, c_void_p, c_void_p]),
     "rg_dqn_head_partials": (c_int, [c_int]),
     "rg_dqn_pair_wave_sums": (c_int, [c_int]),

@@ -1,8 +1,8 @@
 """Batch containers with the field names of the reference's ``reagent.core.types`` ("rlt").
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
-ActorOutput (:245-249), BaseInput (:688-769), DiscreteDqnInput (:772-816), PolicyNetworkInput
-(:899-915) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ActorOutput (:245-249), BaseInput (:688-769), DiscreteDqnInput (:772-816), ParametricDqnInput (:866-896),
+PolicyNetworkInput (:899-915) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -83,6 +83,13 @@ class FeatureData(TensorDataClass):
         ff = self.float_features
         if isinstance(ff, torch.Tensor) and ff.ndim != 2:
             raise ValueError(f"float_features should be 2D; got {ff.shape}.")
+
+    def get_tiled_batch(self, num_tiles: int):
+        """:349-364 — tiled[i * num_tiles:(i + 1) * num_tiles] == float_features[i].  A utility entry point: the
+        parametric DQN step reads the tiled rows in place (rg_mlp_desc.x_tile / rg_tile_concat) and never builds them."""
+        feat = self.float_features
+        assert len(feat.shape) == 2, f"Need feat shape to be (batch_size, feature_dim), got {feat.shape}."
+        return FeatureData(float_features=feat.repeat_interleave(repeats=num_tiles, dim=0))
 
 
 @dataclass
@@ -174,6 +181,37 @@ class DiscreteDqnInput(BaseInput):
 
 
 @dataclass
+class ParametricDqnInput(BaseInput):
+    action: FeatureData
+    next_action: FeatureData
+    possible_actions: FeatureData
+    possible_actions_mask: torch.Tensor
+    possible_next_actions: FeatureData
+    possible_next_actions_mask: torch.Tensor
+    extras: Optional[ExtraData] = None
+    weight: Optional[torch.Tensor] = None
+
+    @classmethod
+    def from_dict(cls, batch):
+        return cls(
+            state=FeatureData(float_features=batch["state_features"]),
+            action=FeatureData(float_features=batch["action"]),
+            next_state=FeatureData(float_features=batch["next_state_features"]),
+            next_action=FeatureData(float_features=batch["next_action"]),
+            possible_actions=FeatureData(float_features=batch["possible_actions"]),
+            possible_actions_mask=batch["possible_actions_mask"],
+            possible_next_actions=FeatureData(float_features=batch["possible_next_actions"]),
+            possible_next_actions_mask=batch["possible_next_actions_mask"],
+            reward=batch["reward"],
+            not_terminal=batch["not_terminal"],
+            time_diff=batch["time_diff"],
+            step=batch["step"],
+            extras=batch["extras"],
+            weight=batch.get("weight", None),
+        )
+
+
+@dataclass
 class PolicyNetworkInput(BaseInput):
     action: FeatureData
     next_action: FeatureData
@@ -211,7 +249,7 @@ USING_REFERENCE_TYPES = False
 _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
-                  "PolicyNetworkInput"):
+                  "ParametricDqnInput", "PolicyNetworkInput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

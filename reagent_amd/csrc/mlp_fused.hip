@@ -123,12 +123,12 @@ __device__ __forceinline__ void mlp_fwd_fused_body(const MlpArgs& a, const PairA
       load_tile_rows_mapped<float, THREADS>(act, pitch, (const float*)a.x, a.ldx, a.rowmap, row_base, a.dims[0], k0p, tid);
     else
       load_tile_rows_mapped<bf16_t, THREADS>(act, pitch, (const bf16_t*)a.x, a.ldx, a.rowmap, row_base, a.dims[0], k0p, tid);
-  } else if (a.x2) {  // two panels (state | action): columns [0, x_split) from x, the rest from x2
+  } else if (a.x2) {  // two panels (state | action): columns [0, x_split) from x (row r / x_tile), the rest from x2
     const int n2 = a.dims[0] - a.x_split;
     if (a.x_is_f32)  // each panel in its own element type (bf16 state rows from the sampler next to fp32 actions)
-      load_tile_to_lds<float, THREADS>(act, pitch, (const float*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid);
+      load_tile_to_lds<float, THREADS>(act, pitch, (const float*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid, a.x_tile);
     else
-      load_tile_to_lds<bf16_t, THREADS>(act, pitch, (const bf16_t*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid);
+      load_tile_to_lds<bf16_t, THREADS>(act, pitch, (const bf16_t*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid, a.x_tile);
     if (a.x2_is_f32)
       load_tile_to_lds<float, THREADS>(act + a.x_split, pitch, (const float*)a.x2, a.ldx2, row_base, a.batch, n2, k0p - a.x_split, tid);
     else
@@ -682,6 +682,10 @@ int rg_mlp_forward_fused(const rg_mlp_desc* d, const void* x, int x_dtype, int64
   if (d->rowmap && (d->x2 || (d->x3 && !d->tile_key) || (batch % 128) != 0)) return RG_EUNSUPPORTED;
   if (d->tile_key && (!d->rowmap || !d->row_begin || d->n_groups <= 0)) return RG_EINVAL;
   if (d->x2 && (d->x_split <= 0 || d->x_split >= d->dims[0] || (d->x_split % 32) != 0)) return RG_EINVAL;
+  if (d->x_tile > 1) {  // tiled state panel: forward only, batch order, plain output layer
+    if (!d->x2) return RG_EINVAL;
+    if (save || d->rowmap || d->tile_key) return RG_EUNSUPPORTED;
+  }
   a.x = x; a.ldx = ldx; a.x_is_f32 = (x_dtype == RG_DT_F32); a.out32 = out32; a.ldo = ldo; a.save = save;
   if (d->x3) return x3_forward_launch(d, a, (hipStream_t)stream);
   size_t lds = (size_t)FB_BM * a.pitch * sizeof(bf16_t);
@@ -727,7 +731,7 @@ int rg_dqn_online_pair_forward(const rg_mlp_desc* d, const void* state, int stat
   // the plain shape only: bf16 operands, one input panel in batch order, a plain 16-wide output layer whose weights fit
   // behind the activation tile (rg_mlp_forward_fused's out_lds condition) with the parked Q rows next to them
   const int L = d->n_layers, KCo = (d->dims[L - 1] + 15) / 16;
-  if (d->x3 || d->x2 || d->rowmap || d->tile_key || L < 2 || d->dims[L] != 16 || KCo < 8 || (KCo & 1)) return RG_EUNSUPPORTED;
+  if (d->x3 || d->x2 || d->x_tile > 1 || d->rowmap || d->tile_key || L < 2 || d->dims[L] != 16 || KCo < 8 || (KCo & 1)) return RG_EUNSUPPORTED;
   for (int l = 0; l + 1 < L; ++l)
     if (d->acts[l] != RG_ACT_RELU) return RG_EUNSUPPORTED;
   if (((uintptr_t)q | (uintptr_t)qn_online | (uintptr_t)qn_target | (uintptr_t)action | (uintptr_t)next_mask | (uintptr_t)dq) & 15)

@@ -38,9 +38,10 @@ __device__ __forceinline__ void split_pack(float v0, float v1, unsigned& hi, uns
 }
 
 // rows [row_base, row_base+64) x cols [0, ncols_pad) of a row-major matrix -> hi / lo LDS planes
+// (xt > 1: source row (row_base + r) / xt, as load_tile_to_lds)
 template <typename T, int THREADS, int LO>
 __device__ __forceinline__ void load_tile_split(bf16_t* act, int pitch, const T* src, long ld, int row_base, int nrows,
-                                                int ncols, int ncols_pad, int tid) {
+                                                int ncols, int ncols_pad, int tid, int xt = 1) {
   const int cpr = ncols_pad / 8;
   const int total = X3_BM * cpr;
   const bool vec = ((ld % 8) == 0) && ((((uintptr_t)src) & 15) == 0);
@@ -56,7 +57,7 @@ __device__ __forceinline__ void load_tile_split(bf16_t* act, int pitch, const T*
         const int cu = c0 + u * THREADS, c = cu < total ? cu : total - 1;
         const int gr = row_base + c / cpr, grow = gr < nrows ? gr : nrows - 1;
         const int kk = (c % cpr) * 8;
-        const T* p = src + (long)grow * ld + (kk < kmax ? kk : kmax);
+        const T* p = src + (long)(xt > 1 ? grow / xt : grow) * ld + (kk < kmax ? kk : kmax);
         raw[u][0] = *(const f32x4*)p;
         if (sizeof(T) == 4) raw[u][sizeof(T) == 4 ? 1 : 0] = *(const f32x4*)(p + 4);
       }
@@ -102,7 +103,7 @@ __device__ __forceinline__ void load_tile_split(bf16_t* act, int pitch, const T*
 #pragma unroll
     for (int e = 0; e < 8; ++e) f[e] = 0.f;
     if (grow < nrows && k0 < ncols) {
-      const T* p = src + (long)grow * ld + k0;
+      const T* p = src + (long)(xt > 1 ? grow / xt : grow) * ld + k0;
       if (vec && k0 + 8 <= ncols) {
         if (sizeof(T) == 4) {
           const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
@@ -533,12 +534,12 @@ __device__ __forceinline__ void mlp_fwd_x3_body(const MlpArgs& a) {
       load_tile_split_mapped<float, THREADS, LO>(act, pitch, (const float*)a.x, a.ldx, a.rowmap, row_base, a.dims[0], k0p, tid);
     else
       load_tile_split_mapped<bf16_t, THREADS, LO>(act, pitch, (const bf16_t*)a.x, a.ldx, a.rowmap, row_base, a.dims[0], k0p, tid);
-  } else if (a.x2) {  // two panels (state | action): columns [0, x_split) from x, the rest from x2
+  } else if (a.x2) {  // two panels (state | action): columns [0, x_split) from x (row r / x_tile), the rest from x2
     const int n2 = a.dims[0] - a.x_split;
     if (a.x_is_f32)
-      load_tile_split<float, THREADS, LO>(act, pitch, (const float*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid);
+      load_tile_split<float, THREADS, LO>(act, pitch, (const float*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid, a.x_tile);
     else
-      load_tile_split<bf16_t, THREADS, LO>(act, pitch, (const bf16_t*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid);
+      load_tile_split<bf16_t, THREADS, LO>(act, pitch, (const bf16_t*)a.x, a.ldx, row_base, a.batch, a.x_split, a.x_split, tid, a.x_tile);
     if (a.x2_is_f32)
       load_tile_split<float, THREADS, LO>(act + a.x_split, pitch, (const float*)a.x2, a.ldx2, row_base, a.batch, n2, k0p - a.x_split, tid);
     else

@@ -63,6 +63,7 @@ struct MlpArgs {
   const void* x2;                 // optional second input panel: columns [x_split, dims[0]) come from here
   long ldx2;
   int x_split;
+  int x_tile;                     // forward, two panels: batch row r reads row r / x_tile of x (1: row r; rg_mlp_desc.x_tile)
   int dx_col0;                    // backward: first input column whose gradient is produced (dx32[0])
   const int* rowmap;              // forward: tile row r reads input row rowmap[r] (-1: zeros); null = identity
   const int* tile_key;            // grouped output layer: FIRST group with rows in each 128-row tile (-1: none), null = plain layer
@@ -136,9 +137,11 @@ __device__ __forceinline__ int frag_row(int h, int e, int lg) {
 
 // ---- LDS tile helpers -----------------------------------------------------------------------
 // rows [row_base, row_base+128) x cols [0, ncols_pad) of a row-major global matrix -> bf16 LDS tile
+// xt > 1: tile row r reads source row (row_base + r) / xt — one source row serves xt consecutive batch rows (the tiled state
+// panel of rg_mlp_desc.x_tile; `nrows` still counts batch rows); the division is per chunk
 template <typename T, int THREADS>
 __device__ __forceinline__ void load_tile_to_lds(bf16_t* act, int pitch, const T* src, long ld, int row_base,
-                                                 int nrows, int ncols, int ncols_pad, int tid) {
+                                                 int nrows, int ncols, int ncols_pad, int tid, int xt = 1) {
   const int cpr = ncols_pad / 8;  // 8-element chunks per row
   const int total = FB_BM * cpr;
   const bool vec = ((ld % 8) == 0) && ((((uintptr_t)src) & 15) == 0);
@@ -156,7 +159,7 @@ __device__ __forceinline__ void load_tile_to_lds(bf16_t* act, int pitch, const T
         const int cu = c0 + u * THREADS, c = cu < total ? cu : total - 1;
         const int gr = row_base + c / cpr, grow = gr < nrows ? gr : nrows - 1;
         const int kk = (c % cpr) * 8;
-        const T* p = src + (long)grow * ld + (kk < kmax ? kk : kmax);
+        const T* p = src + (long)(xt > 1 ? grow / xt : grow) * ld + (kk < kmax ? kk : kmax);
         raw[u][0] = *(const f32x4*)p;
         if (sizeof(T) == 4) raw[u][sizeof(T) == 4 ? 1 : 0] = *(const f32x4*)(p + 4);
       }
@@ -186,7 +189,7 @@ __device__ __forceinline__ void load_tile_to_lds(bf16_t* act, int pitch, const T
     const int grow = row_base + r;
     u16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
     if (grow < nrows && k0 < ncols) {
-      const T* p = src + (long)grow * ld + k0;
+      const T* p = src + (long)(xt > 1 ? grow / xt : grow) * ld + k0;
       if (sizeof(T) == 2 && vec && k0 + 8 <= ncols) {
         v = *(const u16x8*)p;
       } else if (sizeof(T) == 4 && vec && k0 + 8 <= ncols) {
@@ -808,6 +811,7 @@ static inline int fill_args(const rg_mlp_desc* d, int batch, MlpArgs& a, int bac
   a.tile_key = d->tile_key; a.row_begin = d->row_begin; a.n_groups = d->n_groups; a.group_stride = backward ? d->group_stride_bwd : d->group_stride_fwd;
   a.out_scatter = d->tile_key ? d->out_scatter : 0;
   a.x2 = d->x2; a.ldx2 = d->ldx2; a.x_split = d->x2 ? d->x_split : 0; a.dx_col0 = d->dx_col0;
+  a.x_tile = (d->x2 && d->x_tile > 1) ? d->x_tile : 1;
   a.x2_is_f32 = d->x2_dtype == RG_DT_F32;
   a.x = nullptr; a.ldx = 0; a.x_is_f32 = 0; a.out32 = nullptr; a.ldo = 0; a.dout32 = nullptr; a.lddo = 0;
   a.dx32 = nullptr; a.lddx = 0; a.save = 0;

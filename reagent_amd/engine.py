@@ -432,6 +432,7 @@ class FusedMLP:
         d.x3 = int(self.x3)
         d.dx_col0 = 0
         d.dx_only = 0
+        d.x_tile = 0
         d.defer_db, d.sum_n, d.sum_run = 0, 0, 0
         d.db_partials, d.sum_in, d.sum_out = None, None, None
         for i, v in enumerate(self.dims):
@@ -451,13 +452,22 @@ class FusedMLP:
         return x32, None  # the kernel reads fp32 (or bf16) rows directly and casts in flight
 
     def forward(self, xc: torch.Tensor, out32: torch.Tensor, save: bool = False, x2: Optional[torch.Tensor] = None,
-                rowmap: Optional[torch.Tensor] = None):
+                rowmap: Optional[torch.Tensor] = None, x_tile: int = 1):
         """x2 (optional): second input panel — the network input is cat(xc, x2) (FullyConnectedCritic's
         cat(state, action), critic.py:79-92) read in place by the kernel; xc.shape[1] must be a multiple of 32.
+        x_tile = M > 1 (with x2, not saving): the stack runs on the x2.shape[0] tiled rows, row r reading row r // M of xc
+        — cat(xc.repeat_interleave(M, 0), x2) without the tiled state being written (rg_mlp_desc.x_tile).
         rowmap (optional, int32, length a multiple of 128): the stack runs on len(rowmap) rows, row r reading input
         row rowmap[r] of xc (-1: zeros) — "grouped space" of qr_engine.py; out32 has len(rowmap) rows."""
         L.require_cuda(xc)
-        B = xc.shape[0] if rowmap is None else rowmap.shape[0]
+        x_tile = int(x_tile)
+        if x_tile > 1:
+            if x2 is None:
+                raise ValueError("x_tile needs the second input panel (x2=)")
+            B = x2.shape[0]
+            assert xc.shape[0] == (B + x_tile - 1) // x_tile and out32.shape[0] == B
+        else:
+            B = xc.shape[0] if rowmap is None else rowmap.shape[0]
         save = int(save)  # 0 / 1 (everything backward + wgrad read) / SAVE_FOR_DX (what a dx-only backward reads)
         self._ensure_ws(B, xc.device, training=bool(save))
         d = self._fill_desc()
@@ -467,6 +477,7 @@ class FusedMLP:
             assert x2.stride(1) == 1 and xc.shape[1] % 32 == 0  # (the panels may differ in element type)
             assert xc.shape[1] + x2.shape[1] == self.dims[0] and x2.shape[0] == B
             d.x2, d.ldx2, d.x_split, d.x2_dtype = x2.data_ptr(), x2.stride(0), xc.shape[1], ops.dt_code(x2.dtype)
+            d.x_tile = x_tile if x_tile > 1 else 0
         else:
             assert xc.shape[1] == self.dims[0]
             d.x2, d.ldx2, d.x_split = None, 0, 0
@@ -474,10 +485,13 @@ class FusedMLP:
             assert rowmap.dtype == torch.int32 and rowmap.is_contiguous() and B % 128 == 0 and out32.shape[0] == B
             L.require_cuda(rowmap)
         d.rowmap = rowmap.data_ptr() if rowmap is not None else None
-        ops._run("rg_mlp_forward_fused", dict(B=B, save=int(save), dims=tuple(self.dims)),
-                 lambda: L.lib().rg_mlp_forward_fused(d, xc.data_ptr(), ops.dt_code(xc.dtype), xc.stride(0), B,
-                                                      out32.data_ptr(), out32.stride(0), save,
-                                                      L.stream_ptr()))
+        try:
+            ops._run("rg_mlp_forward_fused", dict(B=B, save=int(save), dims=tuple(self.dims)),
+                     lambda: L.lib().rg_mlp_forward_fused(d, xc.data_ptr(), ops.dt_code(xc.dtype), xc.stride(0), B,
+                                                          out32.data_ptr(), out32.stride(0), save,
+                                                          L.stream_ptr()))
+        finally:
+            d.x_tile = 0
         self._saved = save
         return out32
 

@@ -8,13 +8,18 @@ import inspect
 import torch
 
 from ...core import types as rlt
-from ...preprocessing.trainer_preprocessor import DiscreteDqnInputMaker, PolicyNetworkInputMaker  # noqa: F401
+from ...preprocessing.trainer_preprocessor import (  # noqa: F401
+    DiscreteDqnInputMaker,
+    ParametricDqnInputMaker,
+    PolicyNetworkInputMaker,
+)
 
 
-# trainer_preprocessor.py:478-484 minus the memory-network / parametric / slate inputs (not on the path)
+# trainer_preprocessor.py:478-484 minus the memory-network / slate inputs (not on the path)
 REPLAY_BUFFER_MAKER_MAP = {
     rlt.DiscreteDqnInput: DiscreteDqnInputMaker,
     rlt.PolicyNetworkInput: PolicyNetworkInputMaker,
+    rlt.ParametricDqnInput: ParametricDqnInputMaker,
 }
 
 

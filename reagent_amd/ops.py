@@ -165,6 +165,19 @@ def td3_target_action(next_actor, noise, noise_variance, noise_clip_range, lo, h
                                               L.stream_ptr()))
 
 
+def tile_concat(x, x2, out, x_tile: int = 1):
+    """out[r] = cat(x[r // x_tile], x2[r]) (fp32; out may be a [rows, S + A] view of a wider workspace): the critic input
+    on the tiled next state, or with x_tile = 1 the plain cat(state, action)"""
+    _chk_dev(x, x2, out)
+    R, A = x2.shape
+    S = x.shape[1]
+    assert x.dtype == x2.dtype == out.dtype == F32 and x_tile >= 1
+    assert x.shape[0] == (R + x_tile - 1) // x_tile and out.shape == (R, S + A)
+    _run("rg_tile_concat", dict(R=R, S=S, A=A, M=int(x_tile)),
+         lambda: L.lib().rg_tile_concat(L.ptr(x), _ld(x), L.ptr(x2), _ld(x2), R, int(x_tile), S, A, L.ptr(out), _ld(out),
+                                        L.stream_ptr()))
+
+
 def transpose_cast(src, dst=None, dst_t=None):
     _chk_dev(src, dst, dst_t)
     rows, cols = src.shape
@@ -504,6 +517,34 @@ def dqn_head(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, 
                                      L.ptr(not_terminal), float(gamma), L.ptr(gamma_exponent), batch, A,
                                      int(double_q), loss_type, L.ptr(dq), L.ptr(loss_partials), L.ptr(next_q),
                                      L.ptr(next_idx), L.ptr(q_sel), L.stream_ptr()))
+
+
+def pdqn_head_partials(batch: int) -> int:
+    return int(L.lib().rg_pdqn_head_partials(batch))
+
+
+def pdqn_head(q, qn_online_all, qn_target_all, next_mask, reward, not_terminal, gamma, gamma_exponent, double_q, loss_type,
+              target, dq, loss_partials, next_q, next_idx=None):
+    """next_mask given: maxq learning over next_mask.shape[1] candidates per state (qn_*_all hold B * M values; the online
+    values are read with double_q only); next_mask None: SARSA, qn_target_all holds the B values of the logged next action"""
+    _chk_dev(q, qn_online_all, qn_target_all, next_mask, reward, not_terminal, gamma_exponent, target, dq, loss_partials,
+             next_q, next_idx)
+    B = q.numel()
+    maxq = next_mask is not None
+    M = next_mask.shape[1] if maxq else 1
+    if maxq:
+        assert next_mask.is_contiguous() and next_mask.dtype == F32 and next_mask.shape == (B, M)
+        assert double_q is False or qn_online_all is not None
+    for t, n in ((q, B), (qn_online_all, B * M), (qn_target_all, B * M), (reward, B), (not_terminal, B), (gamma_exponent, B),
+                 (target, B), (dq, B), (next_q, B)):
+        assert t is None or (t.is_contiguous() and t.dtype == F32 and t.numel() == n)
+    assert next_idx is None or (next_idx.is_contiguous() and next_idx.dtype == torch.int64 and next_idx.numel() == B)
+    assert loss_partials.dtype == F32 and loss_partials.numel() >= pdqn_head_partials(B)
+    _run("rg_pdqn_head", dict(B=B, M=M),
+         lambda: L.lib().rg_pdqn_head(L.ptr(q), L.ptr(qn_online_all) if maxq else None, L.ptr(qn_target_all),
+                                      L.ptr(next_mask), L.ptr(reward), L.ptr(not_terminal), float(gamma),
+                                      L.ptr(gamma_exponent), B, M, int(maxq), int(bool(double_q)), loss_type, L.ptr(target),
+                                      L.ptr(dq), L.ptr(loss_partials), L.ptr(next_q), L.ptr(next_idx), L.stream_ptr()))
 
 
 def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, reward, extra_metrics,

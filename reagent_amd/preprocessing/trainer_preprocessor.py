@@ -62,6 +62,41 @@ class DiscreteDqnInputMaker:
         )
 
 
+class ParametricDqnInputMaker:
+    """trainer_preprocessor.py:370-413: a discrete action space as a parametric one, every action its one-hot vector
+    and every state offered all of them (get_possible_actions_for_gym, :357-367).  The one-hot / not_terminal /
+    exp(log_prob) work is DiscreteDqnInputMaker's launch; the identity tiles and all-ones masks are constants built with
+    the batch (not on the training step)."""
+
+    def __init__(self, num_actions: int):
+        self.num_actions = num_actions
+        self._discrete = DiscreteDqnInputMaker(num_actions)
+
+    @classmethod
+    def create_for_env(cls, env):
+        space = env.action_space
+        assert hasattr(space, "n"), f"a discrete action space (with `n`) is needed, got {type(space)}"
+        return cls(int(space.n))
+
+    def __call__(self, batch):
+        assert len(batch.state.shape) == 2, f"{batch.state.shape} is not (batch_size, state_dim)."
+        d = self._discrete(batch)
+        B, A, dev = batch.state.shape[0], self.num_actions, batch.state.device
+        possible_actions = torch.eye(A, device=dev).repeat(repeats=(B, 1))
+        mask = torch.ones((B, A), device=dev)
+        return rlt.ParametricDqnInput(
+            state=rlt.FeatureData(float_features=batch.state), action=rlt.FeatureData(float_features=d.action),
+            next_state=rlt.FeatureData(float_features=batch.next_state),
+            next_action=rlt.FeatureData(float_features=d.next_action),
+            possible_actions=rlt.FeatureData(float_features=possible_actions), possible_actions_mask=mask,
+            possible_next_actions=rlt.FeatureData(float_features=possible_actions.clone()),
+            possible_next_actions_mask=mask.clone(), reward=batch.reward, not_terminal=d.not_terminal, step=None,
+            time_diff=None,
+            extras=rlt.ExtraData(mdp_id=None, sequence_number=None, action_probability=d.extras.action_probability,
+                                 max_num_actions=None, metrics=None),
+        )
+
+
 def rescale_actions(actions, new_min, new_max, prev_min, prev_max):
     """reagent/training/utils.py:13-29 (range asserts dropped: they force a host sync)."""
     prev_range = prev_max - prev_min

@@ -56,6 +56,55 @@ def policy_batch(batch: int, state_dim: int, action_dim: int, seed: int = 0,
     )
 
 
+def parametric_batch(batch: int, state_dim: int, action_dim: int, max_num_actions: int, seed: int = 0,
+                     p_terminal: float = 0.1, p_impossible: float = 0.0, n_fully_masked: int = 0,
+                     with_steps: bool = False) -> Dict[str, torch.Tensor]:
+    """Fields of rlt.ParametricDqnInput as a plain dict of CPU fp32 tensors: every state has max_num_actions candidate
+    actions (feature vectors, [batch * max_num_actions, action_dim], state-major) and a mask over them.  The first
+    n_fully_masked states have no possible next action and are terminal (a non-terminal one would put the -1e9 penalty
+    into the TD target); every other state keeps at least one."""
+    g = torch.Generator().manual_seed(seed)
+    M = max_num_actions
+    state = torch.randn(batch, state_dim, generator=g)
+    next_state = torch.randn(batch, state_dim, generator=g)
+    reward = torch.rand(batch, 1, generator=g)
+    not_terminal = (torch.rand(batch, 1, generator=g) > p_terminal).float()
+    pa = torch.rand(batch * M, action_dim, generator=g) * 2.0 - 1.0
+    pna = torch.rand(batch * M, action_dim, generator=g) * 2.0 - 1.0
+    action = pa.reshape(batch, M, action_dim)[torch.arange(batch), torch.randint(M, (batch,), generator=g)].clone()
+    next_action = pna.reshape(batch, M, action_dim)[torch.arange(batch), torch.randint(M, (batch,), generator=g)].clone()
+    pnm = torch.ones(batch, M)
+    if p_impossible > 0:
+        pnm = (torch.rand(batch, M, generator=g) >= p_impossible).float()
+        pnm[torch.arange(batch), torch.randint(M, (batch,), generator=g)] = 1.0
+    if n_fully_masked:
+        pnm[:n_fully_masked] = 0.0
+        not_terminal[:n_fully_masked] = 0.0
+    if with_steps:
+        step = torch.randint(1, 4, (batch, 1), generator=g).float()
+        time_diff = torch.randint(1, 5, (batch, 1), generator=g).float()
+    else:
+        step, time_diff = torch.ones(batch, 1), torch.ones(batch, 1)
+    return dict(state=state, next_state=next_state, reward=reward, not_terminal=not_terminal, action=action,
+                next_action=next_action, possible_actions=pa, possible_actions_mask=torch.ones(batch, M),
+                possible_next_actions=pna, possible_next_actions_mask=pnm, step=step, time_diff=time_diff)
+
+
+def to_parametric_input(d: Dict[str, torch.Tensor], device=None):
+    from .core import types as rlt
+
+    t = (lambda x: x.to(device)) if device is not None else (lambda x: x)
+    fd = lambda k: rlt.FeatureData(t(d[k]))  # noqa: E731
+    return rlt.ParametricDqnInput(
+        state=fd("state"), next_state=fd("next_state"), reward=t(d["reward"]), time_diff=t(d["time_diff"]),
+        step=t(d["step"]), not_terminal=t(d["not_terminal"]), action=fd("action"), next_action=fd("next_action"),
+        possible_actions=fd("possible_actions"), possible_actions_mask=t(d["possible_actions_mask"]),
+        possible_next_actions=fd("possible_next_actions"),
+        possible_next_actions_mask=t(d["possible_next_actions_mask"]),
+        extras=rlt.ExtraData(metrics=t(d["metrics"]) if "metrics" in d else None),
+    )
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 

@@ -5,10 +5,12 @@ from .sac_trainer import CRRWeightFn, SACTrainer  # noqa: F401
 from .td3_trainer import TD3Trainer  # noqa: F401
 from .c51_trainer import C51Trainer  # noqa: F401
 from .discrete_crr_trainer import DiscreteCRRTrainer  # noqa: F401
+from .parametric_dqn_trainer import ParametricDQNTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
     CRRTrainerParameters,
     DQNTrainerParameters,
+    ParametricDQNTrainerParameters,
     QRDQNTrainerParameters,
     SACTrainerParameters,
     TD3TrainerParameters,

@@ -18,6 +18,7 @@ from ..optimizer import Optimizer__Union
 from .c51_trainer import C51Trainer
 from .discrete_crr_trainer import DiscreteCRRTrainer
 from .dqn_trainer import DQNTrainer
+from .parametric_dqn_trainer import ParametricDQNTrainer
 from .qrdqn_trainer import QRDQNTrainer
 from .sac_trainer import SACTrainer
 from .td3_trainer import TD3Trainer
@@ -80,6 +81,11 @@ class TD3TrainerParameters:
     "q2_network_target", "q_network_cpe", "q_network_cpe_target", "metrics_to_score", "evaluation"])
 class CRRTrainerParameters:
     """parameters.py:44-62"""
+
+
+@make_config_class(ParametricDQNTrainer.__init__, blocklist=["use_gpu", "q_network", "q_network_target", "reward_network"])
+class ParametricDQNTrainerParameters:
+    """parameters.py:71-76"""
 
 
 @make_config_class(DQNTrainer.__init__, blocklist=[
