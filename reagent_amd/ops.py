@@ -559,6 +559,8 @@ def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, 
     for t in (next_scores, next_mask, action):
         assert t.is_contiguous() and t.dtype == F32 and t.shape == (batch, A)
     assert extra_metrics is None or (extra_metrics.is_contiguous() and extra_metrics.shape == (batch, M - 1))
+    for t in (reward_partials, cpe_partials):  # one partial per workgroup of 256 transitions
+        assert t.is_contiguous() and t.dtype == F32 and t.numel() >= dqn_head_partials(batch)
     _run("rg_cpe_head", dict(B=batch, A=A, M=M),
          lambda: L.lib().rg_cpe_head(L.ptr(reward_est), L.ptr(q_cpe), L.ptr(q_cpe_tgt_next), L.ptr(next_scores),
                                      L.ptr(next_mask), L.ptr(action), L.ptr(reward), L.ptr(extra_metrics),
