@@ -612,6 +612,47 @@ int rg_pdqn_head(const float* q, const float* qn_online_all, const float* qn_tar
                  int max_num_actions, int maxq, int double_q, int loss_type, float* target, float* dq,
                  float* loss_partials, float* next_q, int64_t* next_idx, rg_stream_t stream);
 
+/* ABI 14 — SlateQ (reagent/training/slate_q_trainer.py): a state has C candidate documents [B, C, D] with a presence
+ * mask [B, C] (one byte per entry: torch.bool storage) and a value [B, C]; a slate is K indices into them [B, K] int64.
+ * rg_slate_gather: DocList.select_slate (reagent/core/types.py:277-284) with _get_docs_value's value * mask
+ * (slate_q_trainer.py:162-164).  out_features[b * K + k, :D] (row pitch ldo: the candidate panel of the critic's forward
+ * or of rg_tile_concat; NULL: the weights alone) = features[b, index[b, k], :], out_weight[b, k] = value * mask of that
+ * document.  Where
+ * not_terminal (nullable, [B]) is 0 every index of the row is read as 0 (_action_docs, :112-117; `index` itself is not
+ * written).  An index outside [0, C) is a caller error, as it is for torch's indexing: it is CLAMPED into range, so no
+ * address outside the arrays is ever formed.  features is contiguous; 16-byte accesses where D, the bases and ldo allow,
+ * scalars elsewhere.  count_mask (nullable, count_n bytes) with count_out: the same launch counts the non-zero bytes —
+ * the true entries of reward_mask — into count_out[0], the device scalar rg_slateq_head reads.
+ * rg_slate_topk: _get_maxq_topk (:145-160).  score[b, c] = q_all[b, c] * w[b, c], w = value * mask, or with
+ * single_selection softmax over the C candidates of value * mask (max-subtracted, divided by the row sum).  next_index
+ * [B, K] = the K largest scores' indices in descending order, of equal scores the LOWER index first (torch.topk leaves
+ * that open; this is torch.sort(descending=True, stable=True)); q_sel [B, K] = q_all at them.  Inputs finite.
+ * 1 <= K <= C <= RG_SLATE_MAX_CANDIDATES, RG_EINVAL beyond.
+ * rg_slateq_head: train_step_gen :204-259 after the forwards.  q, qn, wn, reward [B, K] fp32 (online critic on the logged
+ * slate, target critic on the next slate, value * mask of the next slate's documents), reward_mask [B, K] bytes,
+ * not_terminal [B].  next_q[b] = sum_k qn * (single_selection ? softmax over the K items of wn : wn); without single
+ * selection divided by min(sum_c norm_mask[b, c], slate_size) (:169-175; norm_mask [B, C] bytes is the current or the
+ * next state's mask, by next_slate_value_norm_method); times not_terminal.  target = reward + discount * next_q,
+ * discount = gamma, or powf(gamma, time_diff[b] / discount_time_scale) when time_diff != NULL (the division in fp32, the
+ * power correctly rounded to fp32).
+ * F.mse_loss: with single selection over the n_selected[0] elements where reward_mask is set (dq = 0 elsewhere),
+ * otherwise over all B * K.  n_selected is DEVICE memory (rg_slate_gather's count_out): no host synchronisation.
+ * Outputs: target, dq [B, K], next_q [B], loss_partials [rg_slateq_head_partials(B)] whose ordered sum is the loss
+ * (already divided by the element count; rg_reduce_sum with scale 1 finishes it). */
+#define RG_SLATE_MAX_CANDIDATES 1024
+int rg_slate_gather(const float* features, const uint8_t* mask, const float* value, const int64_t* index,
+                    const float* not_terminal, int batch, int num_candidates, int slate_size, int feature_dim,
+                    float* out_features, int64_t ldo, float* out_weight, const uint8_t* count_mask, int64_t count_n,
+                    int32_t* count_out, rg_stream_t stream);
+int rg_slate_topk(const float* q_all, const float* value, const uint8_t* mask, int batch, int num_candidates, int slate_size,
+                  int single_selection, int64_t* next_index, float* q_sel, rg_stream_t stream);
+int rg_slateq_head_partials(int batch);
+int rg_slateq_head(const float* q, const float* qn, const float* wn, const float* reward, const uint8_t* reward_mask,
+                   const float* not_terminal, double gamma, const float* time_diff, double discount_time_scale,
+                   int single_selection, const uint8_t* norm_mask, int num_candidates, int slate_size,
+                   const int32_t* n_selected, int batch, int num_items, float* target, float* dq, float* loss_partials,
+                   float* next_q, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -1,10 +1,22 @@
 """Parameter dataclasses with the field names / defaults of reagent/core/parameters.py
-(RLParameters :46-67, EvaluationParameters :118-120, NormalizationParameters :138-152).
+(SlateOptParameters :33-43, RLParameters :46-67, EvaluationParameters :118-120, NormalizationParameters :138-152).
 Objects of the reference's own classes are accepted anywhere these are (duck typing)."""
+import enum
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
 
 CONTINUOUS_TRAINING_ACTION_RANGE = (-1.0, 1.0)
+
+
+class SlateOptMethod(enum.Enum):
+    GREEDY = "greedy"
+    TOP_K = "top_k"
+    EXACT = "exact"
+
+
+@dataclass(frozen=True)
+class SlateOptParameters:
+    method: SlateOptMethod = SlateOptMethod.TOP_K
 
 
 @dataclass(frozen=True)

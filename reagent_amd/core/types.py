@@ -1,8 +1,8 @@
 """Batch containers with the field names of the reference's ``reagent.core.types`` ("rlt").
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
-ActorOutput (:245-249), BaseInput (:688-769), DiscreteDqnInput (:772-816), ParametricDqnInput (:866-896),
-PolicyNetworkInput (:899-915) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -67,6 +67,33 @@ class ActorOutput(TensorDataClass):
     action: torch.Tensor
     log_prob: Optional[torch.Tensor] = None
     squashed_mean: Optional[torch.Tensor] = None
+
+
+@dataclass
+class DocList(TensorDataClass):
+    # (batch_size, num_candidates, num_document_features)
+    float_features: torch.Tensor
+    # (batch_size, num_candidates): whether the candidate is present (torch.bool), and a context dependent value (an
+    # action probability, or the document's score from another model)
+    mask: torch.Tensor = None
+    value: torch.Tensor = None
+
+    def __post_init__(self):
+        assert len(self.float_features.shape) == 3, f"Unexpected shape: {self.float_features.shape}"
+        if self.mask is None:
+            self.mask = self.float_features.new_ones(self.float_features.shape[:2], dtype=torch.bool)
+        if self.value is None:
+            self.value = self.float_features.new_ones(self.float_features.shape[:2])
+
+    @torch.no_grad()
+    def select_slate(self, action: torch.Tensor):
+        """:277-284.  A utility entry point: the SlateQ step gathers with rg_slate_gather and never builds this."""
+        row_idx = torch.repeat_interleave(torch.arange(action.shape[0], device=action.device).unsqueeze(1), action.shape[1], dim=1)
+        return DocList(self.float_features[row_idx, action], self.mask[row_idx, action], self.value[row_idx, action])
+
+    def as_feature_data(self):
+        _batch_size, _slate_size, feature_dim = self.float_features.shape
+        return FeatureData(self.float_features.view(-1, feature_dim))
 
 
 @dataclass
@@ -181,6 +208,38 @@ class DiscreteDqnInput(BaseInput):
 
 
 @dataclass
+class SlateQInput(BaseInput):
+    """reward, reward_mask: (batch_size, slate_size); reward_mask says whether the item's reward could be observed"""
+
+    action: torch.Tensor
+    next_action: torch.Tensor
+    reward_mask: torch.Tensor
+    extras: Optional[ExtraData] = None
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(
+            state=FeatureData(
+                float_features=d["state_features"],
+                candidate_docs=DocList(float_features=d["candidate_features"], mask=d["item_mask"], value=d["item_probability"]),
+            ),
+            next_state=FeatureData(
+                float_features=d["next_state_features"],
+                candidate_docs=DocList(float_features=d["next_candidate_features"], mask=d["next_item_mask"],
+                                       value=d["next_item_probability"]),
+            ),
+            action=d["action"],
+            next_action=d["next_action"],
+            reward=d["position_reward"],
+            reward_mask=d["reward_mask"],
+            time_diff=d["time_diff"],
+            not_terminal=d["not_terminal"],
+            step=None,
+            extras=ExtraData.from_dict(d),
+        )
+
+
+@dataclass
 class ParametricDqnInput(BaseInput):
     action: FeatureData
     next_action: FeatureData
@@ -248,8 +307,8 @@ def _reference_types():
 USING_REFERENCE_TYPES = False
 _ref = _reference_types()
 if _ref is not None:
-    for _name in ("TensorDataClass", "ActorOutput", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
-                  "ParametricDqnInput", "PolicyNetworkInput"):
+    for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
+                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

@@ -547,6 +547,79 @@ def pdqn_head(q, qn_online_all, qn_target_all, next_mask, reward, not_terminal, 
                                       L.ptr(dq), L.ptr(loss_partials), L.ptr(next_q), L.ptr(next_idx), L.stream_ptr()))
 
 
+def _u8(t):
+    """a bool / uint8 tensor as its bytes (torch.bool storage is one byte per entry)"""
+    if t is None:
+        return None
+    assert t.dtype in (torch.bool, torch.uint8) and t.is_contiguous()
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def slate_gather(features, mask, value, index, out_features, out_weight, not_terminal=None, count_mask=None, count_out=None):
+    """out_features[b * K + k] = features[b, index[b, k]] (a [B * K, D] view, e.g. of a wider workspace), out_weight[b, k] =
+    (value * mask)[b, index[b, k]]; rows with not_terminal == 0 read document 0 (index is left as it is).  out_features None:
+    the weights alone.  count_mask with count_out (int32 [1]): the launch also counts count_mask's true entries into count_out"""
+    _chk_dev(features, mask, value, index, out_features, out_weight, not_terminal, count_mask, count_out)
+    B, C, D = features.shape
+    K = index.shape[1]
+    assert features.dtype == value.dtype == out_weight.dtype == F32
+    assert features.is_contiguous() and value.is_contiguous() and value.shape == (B, C) and mask.shape == (B, C)
+    assert index.dtype == torch.int64 and index.is_contiguous() and index.shape == (B, K)
+    assert out_features is None or (out_features.dtype == F32 and out_features.shape == (B * K, D))
+    assert out_weight.is_contiguous() and out_weight.numel() == B * K
+    assert not_terminal is None or (not_terminal.dtype == F32 and not_terminal.is_contiguous() and not_terminal.numel() == B)
+    assert (count_mask is None) == (count_out is None)
+    assert count_out is None or (count_out.dtype == torch.int32 and count_out.numel() >= 1)
+    m, cm = _u8(mask), _u8(count_mask)
+    _run("rg_slate_gather", dict(B=B, C=C, K=K, D=D),
+         lambda: L.lib().rg_slate_gather(L.ptr(features), L.ptr(m), L.ptr(value), L.ptr(index), L.ptr(not_terminal), B, C, K, D,
+                                         L.ptr(out_features), _ld(out_features) if out_features is not None else 0,
+                                         L.ptr(out_weight), L.ptr(cm),
+                                         cm.numel() if cm is not None else 0, L.ptr(count_out), L.stream_ptr()))
+
+
+def slate_topk(q_all, value, mask, single_selection: bool, next_index, q_sel):
+    """next_index [B, K] = the K candidates with the largest q_all * (value * mask, or its softmax over the candidates with
+    single_selection), descending, the lower index first among equal scores; q_sel = q_all at them"""
+    _chk_dev(q_all, value, mask, next_index, q_sel)
+    B, C = value.shape
+    K = next_index.shape[1]
+    assert q_all.dtype == value.dtype == q_sel.dtype == F32 and next_index.dtype == torch.int64
+    assert q_all.is_contiguous() and q_all.numel() == B * C and value.is_contiguous() and mask.shape == (B, C)
+    assert next_index.is_contiguous() and next_index.shape == (B, K) and q_sel.is_contiguous() and q_sel.numel() == B * K
+    m = _u8(mask)
+    _run("rg_slate_topk", dict(B=B, C=C, K=K),
+         lambda: L.lib().rg_slate_topk(L.ptr(q_all), L.ptr(value), L.ptr(m), B, C, K, int(bool(single_selection)),
+                                       L.ptr(next_index), L.ptr(q_sel), L.stream_ptr()))
+
+
+def slateq_head_partials(batch: int) -> int:
+    return int(L.lib().rg_slateq_head_partials(batch))
+
+
+def slateq_head(q, qn, wn, reward, reward_mask, not_terminal, gamma, time_diff, discount_time_scale, single_selection: bool,
+                norm_mask, slate_size, n_selected, target, dq, loss_partials, next_q):
+    """the SlateQ TD head over [B, K] items; time_diff None: the discount is gamma.  single_selection reads reward_mask and
+    the device count n_selected (int32 [1]), otherwise norm_mask [B, C] and slate_size form the divisor.  The ordered sum of
+    loss_partials is the loss"""
+    _chk_dev(q, qn, wn, reward, reward_mask, not_terminal, time_diff, norm_mask, n_selected, target, dq, loss_partials, next_q)
+    B, K = reward.shape
+    for t, n in ((q, B * K), (qn, B * K), (wn, B * K), (reward, B * K), (not_terminal, B), (time_diff, B), (target, B * K),
+                 (dq, B * K), (next_q, B)):
+        assert t is None or (t.is_contiguous() and t.dtype == F32 and t.numel() == n)
+    assert reward_mask is None or reward_mask.shape == (B, K)
+    assert norm_mask is None or (norm_mask.dim() == 2 and norm_mask.shape[0] == B)
+    assert n_selected is None or n_selected.dtype == torch.int32
+    assert loss_partials.dtype == F32 and loss_partials.numel() >= slateq_head_partials(B)
+    rm, nm = _u8(reward_mask), _u8(norm_mask)
+    C = norm_mask.shape[1] if norm_mask is not None else 0
+    _run("rg_slateq_head", dict(B=B, K=K),
+         lambda: L.lib().rg_slateq_head(L.ptr(q), L.ptr(qn), L.ptr(wn), L.ptr(reward), L.ptr(rm), L.ptr(not_terminal),
+                                        float(gamma), L.ptr(time_diff), float(discount_time_scale or 0.0),
+                                        int(bool(single_selection)), L.ptr(nm), C, int(slate_size), L.ptr(n_selected), B, K,
+                                        L.ptr(target), L.ptr(dq), L.ptr(loss_partials), L.ptr(next_q), L.stream_ptr()))
+
+
 def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, reward, extra_metrics,
              not_terminal, gamma, gamma_exponent, temperature, num_metrics, loss_type, d_reward_est, d_q_cpe,
              reward_partials, cpe_partials, propensities_out=None):

@@ -105,6 +105,53 @@ def to_parametric_input(d: Dict[str, torch.Tensor], device=None):
     )
 
 
+def slateq_batch(batch: int, state_dim: int, doc_dim: int, num_candidates: int, slate_size: int, seed: int = 0,
+                 p_terminal: float = 0.1, p_absent: float = 0.3, n_terminal: int = 2, n_sparse: int = 2,
+                 with_time_diff: bool = False) -> Dict[str, torch.Tensor]:
+    """Fields of rlt.SlateQInput as a plain dict of CPU tensors under the keys rlt.SlateQInput.from_dict reads: every state
+    and next state has num_candidates documents (features, a boolean presence mask, a value in (0.05, 1]) and a logged slate
+    of slate_size indices into them, drawn over ALL candidates (padded documents get selected).  Every state keeps at least
+    one present document.  The first n_terminal rows are terminal with a non-zero first next_action index; the n_sparse
+    rows after them have fewer than slate_size present documents in state and next state (slate_size > 1); the last row's
+    reward_mask is all false and the one before it has a true entry."""
+    g = torch.Generator().manual_seed(seed)
+    B, C, K = batch, num_candidates, slate_size
+    assert C >= 2 and B >= n_terminal + n_sparse + 2
+
+    def docs():
+        features = torch.rand(B, C, doc_dim, generator=g) * 2.0 - 1.0
+        mask = torch.rand(B, C, generator=g) >= p_absent
+        mask[torch.arange(B), torch.randint(C, (B,), generator=g)] = True
+        for i in range(n_terminal, n_terminal + n_sparse):
+            mask[i] = False
+            mask[i, torch.randperm(C, generator=g)[:1 + (i % max(K - 1, 1))]] = True
+        return features, mask, 0.05 + 0.95 * torch.rand(B, C, generator=g)
+
+    cand, item_mask, item_prob = docs()
+    next_cand, next_item_mask, next_item_prob = docs()
+    not_terminal = (torch.rand(B, 1, generator=g) > p_terminal).float()
+    action = torch.randint(C, (B, K), generator=g)
+    next_action = torch.randint(C, (B, K), generator=g)
+    not_terminal[:n_terminal] = 0.0
+    not_terminal[n_terminal:n_terminal + n_sparse] = 1.0
+    next_action[:n_terminal, 0] = 1 + torch.randint(C - 1, (n_terminal,), generator=g)
+    reward_mask = torch.rand(B, K, generator=g) > 0.5
+    reward_mask[B - 1] = False
+    reward_mask[B - 2, 0] = True
+    time_diff = torch.randint(1, 5, (B, 1), generator=g).float() if with_time_diff else torch.ones(B, 1)
+    return dict(state_features=torch.randn(B, state_dim, generator=g), next_state_features=torch.randn(B, state_dim, generator=g),
+                candidate_features=cand, next_candidate_features=next_cand, item_mask=item_mask, next_item_mask=next_item_mask,
+                item_probability=item_prob, next_item_probability=next_item_prob, action=action, next_action=next_action,
+                position_reward=torch.rand(B, K, generator=g), reward_mask=reward_mask, time_diff=time_diff,
+                not_terminal=not_terminal)
+
+
+def to_slateq_input(d: Dict[str, torch.Tensor], device=None):
+    from .core import types as rlt
+
+    return rlt.SlateQInput.from_dict({k: (v.to(device) if device is not None else v) for k, v in d.items()})
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 

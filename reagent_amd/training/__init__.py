@@ -6,6 +6,7 @@ from .td3_trainer import TD3Trainer  # noqa: F401
 from .c51_trainer import C51Trainer  # noqa: F401
 from .discrete_crr_trainer import DiscreteCRRTrainer  # noqa: F401
 from .parametric_dqn_trainer import ParametricDQNTrainer  # noqa: F401
+from .slate_q_trainer import NextSlateValueNormMethod, SlateQTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
     CRRTrainerParameters,
@@ -13,5 +14,6 @@ from .parameters import (  # noqa: F401
     ParametricDQNTrainerParameters,
     QRDQNTrainerParameters,
     SACTrainerParameters,
+    SlateQTrainerParameters,
     TD3TrainerParameters,
 )

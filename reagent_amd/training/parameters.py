@@ -13,7 +13,7 @@ import dataclasses
 import inspect
 from typing import get_args
 
-from ..core.parameters import RLParameters
+from ..core.parameters import EvaluationParameters, RLParameters
 from ..optimizer import Optimizer__Union
 from .c51_trainer import C51Trainer
 from .discrete_crr_trainer import DiscreteCRRTrainer
@@ -21,6 +21,7 @@ from .dqn_trainer import DQNTrainer
 from .parametric_dqn_trainer import ParametricDQNTrainer
 from .qrdqn_trainer import QRDQNTrainer
 from .sac_trainer import SACTrainer
+from .slate_q_trainer import SlateQTrainer
 from .td3_trainer import TD3Trainer
 
 _FACTORY_BY_TYPE = {RLParameters: RLParameters, Optimizer__Union: Optimizer__Union.default}
@@ -36,17 +37,19 @@ def _factory_for(name, annotation):
     return None
 
 
-def make_config_class(func, blocklist):
+def make_config_class(func, blocklist, factories=None):
     """decorator: a dataclass whose fields are `func`'s annotated parameters outside `blocklist`
-    (reagent/core/configuration.py:40-103), with `asdict()` = the keyword arguments to pass on"""
+    (reagent/core/configuration.py:40-103), with `asdict()` = the keyword arguments to pass on.  `factories`: the default
+    factory of a None-defaulted parameter by name, where the constructor's default is not its type's"""
     blocked = set(blocklist) | {"self"}
+    factories = factories or {}
 
     def wrap(cls):
         fields = []
         for p in inspect.signature(func).parameters.values():
             if p.name in blocked or (p.annotation is inspect.Parameter.empty and p.default is inspect.Parameter.empty):
                 continue  # (configuration.py:75-83: a parameter needs an annotation or a default to become a field)
-            factory = _factory_for(p.name, p.annotation) if p.default in (None, "default") else None
+            factory = (factories.get(p.name) or _factory_for(p.name, p.annotation)) if p.default in (None, "default") else None
             if factory is not None:
                 fields.append((p.name, p.annotation, dataclasses.field(default_factory=factory)))
             elif p.annotation is inspect.Parameter.empty:
@@ -81,6 +84,13 @@ class TD3TrainerParameters:
     "q2_network_target", "q_network_cpe", "q_network_cpe_target", "metrics_to_score", "evaluation"])
 class CRRTrainerParameters:
     """parameters.py:44-62"""
+
+
+@make_config_class(SlateQTrainer.__init__, blocklist=["use_gpu", "q_network", "q_network_target"],
+                   factories=dict(rl=lambda: RLParameters(maxq_learning=False),
+                                  evaluation=lambda: EvaluationParameters(calc_cpe_in_training=False)))
+class SlateQTrainerParameters:
+    """parameters.py:64-68 (slate_size carries neither annotation nor default: not a field, as in the reference)"""
 
 
 @make_config_class(ParametricDQNTrainer.__init__, blocklist=["use_gpu", "q_network", "q_network_target", "reward_network"])
