@@ -35,7 +35,7 @@ nn_, nc = torch.randn(B, A), torch.randn(B, A)
 batch = synthetic.to_policy_input(b, dev)
 tr.train_step_native(batch, nn_, nc)
 torch.cuda.synchronize()
-ours = [gr.cpu().clone() for gr in tr._e["actor"]["slab"].grad_views()]
+ours = [gr.cpu().clone() for gr in tr._e["actor"].slab.grad_views()]
 res = {}
 for name, dt in (("f32", torch.float32), ("f64", torch.float64)):
     cast = lambda ws: [w.to(dt) for w in ws]

@@ -160,7 +160,7 @@ class _GraphedLoop:
         launches the queue idles ~8 us (between two kernels of a stream ~1 us); the cursor and the Adam step count live on the
         device and advance per captured step, so nothing else changes.  Must divide index_pool_steps; `replay.steps` tells
         the caller how many steps a call makes."""
-        from .training.dqn_trainer import enable_graph_mode
+        from .training.plumbing import enable_graph_mode
 
         tr = self.trainer
         dev = torch.device(self.rb.device)
@@ -315,14 +315,14 @@ class _GraphedLoop:
 
     def release_graph(self):
         """drop the captured graph(s) and return the optimizers to scalar-argument launches"""
-        from .training.dqn_trainer import disable_graph_mode
+        from .training.plumbing import disable_graph_mode
 
         self.flush()
         self._graph = None
         disable_graph_mode(self.trainer)
 
     def _flush_graph(self):
-        from .training.dqn_trainer import note_graph_replays
+        from .training.plumbing import note_graph_replays
 
         self._join_update()
         note_graph_replays(self.trainer, self._replays)

@@ -17,13 +17,13 @@ from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
 from ..core.parameters import EvaluationParameters, RLParameters
-from ..engine import ensure_slab
 from ..optimizer import Optimizer__Union, SoftUpdate
-from .dqn_trainer import _CpeEngine, _SegmentLoss, dp_reduce, held_gradients, native_step, publish_gradients
+from .dqn_trainer import _CpeEngine
 from .dqn_trainer_base import DQNTrainerBaseLightning
+from .plumbing import NativeStepMixin, native_step
 
 
-class DiscreteCRRTrainer(DQNTrainerBaseLightning):
+class DiscreteCRRTrainer(NativeStepMixin, DQNTrainerBaseLightning):
     """Critic Regularized Regression (https://arxiv.org/abs/2006.15134), discrete actions."""
 
     def __init__(
@@ -76,7 +76,6 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         self.clip_limit = clip_limit
         self.max_weight = max_weight
         self._ws_batch = -1
-        self._dp_group, self._dp_world = None, 1
         self._native_idx = 0
         self._cpe = _CpeEngine(self) if self.calc_cpe_in_training else None
 
@@ -111,21 +110,10 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         return optimizers
 
     # ---- engine ----------------------------------------------------------------------------------
-    @staticmethod
-    def _f32c(t: torch.Tensor) -> torch.Tensor:
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
-    @staticmethod
-    def _net_in(t: torch.Tensor) -> torch.Tensor:
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            t = t.float()
-        return t if t.stride(-1) == 1 and t.is_contiguous() else t.contiguous()
-
     def _engine(self, B, dev):
         A = self.num_actions
         nets = dict(actor=self.actor_network, q1=self.q1_network, q2=self.q2_network)
-        self._e = {k: _CpeEngine._net_engine(n) for k, n in nets.items() if n is not None}
+        self._e = {k: self._trainable(n) for k, n in nets.items() if n is not None}
         tg = dict(actor=self.actor_network_target, q1=self.q1_network_target,
                   q2=getattr(self, "q2_network_target", None))
         self._t = {k: n.fc.stack() for k, n in tg.items() if n is not None}
@@ -139,12 +127,6 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
             self._losses = {n: torch.empty(1, **f) for n in ("q1", "q2", "plain", "entropy", "actor")}
             self._ws_batch = B
 
-    def _publish(self, e, held=()):
-        slab = e["slab"]
-        if self._dp_group is not None:
-            dp_reduce(self, slab)
-        publish_gradients(slab, e["params"], held)
-
     # ---- segments --------------------------------------------------------------------------------
     def _critic_forward(self, b):
         state, next_state = self._net_in(b.state.float_features), self._net_in(b.next_state.float_features)
@@ -155,7 +137,7 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         has_q2 = "q2" in e
         for k in ("q1", "q2"):
             if k in e:
-                e[k]["stack"].stage_weights(need_transposed=True)
+                e[k].stack.stage_weights(need_transposed=True)
                 t[k].stage_weights(need_transposed=False)
         # next_q_values = q1_network_target(next_state) (:307); compute_target_q_values (:191-206)
         xn, _ = t["q1"].stage_input(next_state, need_transposed=False)
@@ -163,7 +145,7 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         if has_q2:
             xn2, _ = t["q2"].stage_input(next_state, need_transposed=False)
             t["q2"].forward(xn2, self._q2n, save=False)
-        next_actor = t["actor"] if self.use_target_actor else e["actor"]["stack"]
+        next_actor = t["actor"] if self.use_target_actor else e["actor"].stack
         next_actor.stage_weights(need_transposed=not self.use_target_actor)
         xa, _ = next_actor.stage_input(next_state, need_transposed=False)
         next_actor.forward(xa, self._next_scores, save=False)
@@ -171,11 +153,11 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         if next_module.exploration_variance is not None:  # `.action` of an exploring actor carries its noise
             self._next_scores.copy_(next_module.explore(self._next_scores)[0])
         # compute_td_loss for both critics (:208-212)
-        q1s = e["q1"]["stack"]
+        q1s = e["q1"].stack
         x1, self._x1_t = q1s.stage_input(state, need_transposed=True)
         q1s.forward(x1, self._q1v, save=True)
         if has_q2:
-            q2s = e["q2"]["stack"]
+            q2s = e["q2"].stack
             x2, self._x2_t = q2s.stage_input(state, need_transposed=True)
             q2s.forward(x2, self._q2v, save=True)
         boosts = self.reward_boosts.reshape(-1) if self._has_reward_boost else None
@@ -193,13 +175,8 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
             ops.reduce_sum(self._parts["q2"], P, 1.0 / B, self._losses["q2"])
 
     def _critic_backward(self, which, grad_out=None):
-        e = self._e[which]
-        dq = self._dq1 if which == "q1" else self._dq2
-        if grad_out is not None:
-            dq = dq * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dq, self._x1_t if which == "q1" else self._x2_t, e["dw"], e["db"])
-        self._publish(e, held)
+        dq, xt = (self._dq1, self._x1_t) if which == "q1" else (self._dq2, self._x2_t)
+        self._e[which].backward(dq, xt, grad_out)
 
     def _actor_forward(self, b, with_loss: bool):
         """all_q_values = q1_network(state) with the weights its optimizer just produced (:327), the
@@ -207,7 +184,7 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         state = self._net_in(b.state.float_features)
         B = state.shape[0]
         e = self._e
-        act = e["actor"]["stack"]
+        act = e["actor"].stack
         act.stage_weights(need_transposed=True)
         xs, self._xs_t = act.stage_input(state, need_transposed=True)
         act.forward(xs, self._raw_scores, save=with_loss)
@@ -218,7 +195,7 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         self.all_action_scores = self._scores
         if not with_loss:
             return
-        q1s = e["q1"]["stack"]
+        q1s = e["q1"].stack
         q1s.stage_weights(need_transposed=True)
         x1, _ = q1s.stage_input(state, need_transposed=False)
         q1s.forward(x1, self._q1_new, save=False)
@@ -240,13 +217,10 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
             self._losses["actor"].copy_(self._losses["plain"])
 
     def _actor_backward(self, grad_out=None):
-        a = self._e["actor"]
         d = self._dscores if grad_out is None else self._dscores * grad_out
         if self._clamp_passes is not None:  # backward of the exploration clamp
             d = d * self._clamp_passes
-        held = held_gradients(a["slab"], a["params"])
-        a["stack"].backward(d, self._xs_t, a["dw"], a["db"], out32=self._raw_scores)
-        self._publish(a, held)
+        self._e["actor"].backward(d, self._xs_t, out32=self._raw_scores)
 
     # ---- CPE hooks (dqn_trainer_base.py:338-452 as called at :354-363) ---------------------------
     def _cpe_next_action_scores(self, next_state, out):
@@ -261,36 +235,23 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         self._check_input(training_batch)
         b = training_batch
         self._critic_forward(b)
-        q1 = self._e["q1"]
-        q1_loss = _SegmentLoss.apply(lambda g: self._critic_backward("q1", g), self._losses["q1"], *q1["params"])
+        q1_loss = self._e["q1"].loss(lambda g: self._critic_backward("q1", g), self._losses["q1"])
         self.log("td_loss", q1_loss.detach(), prog_bar=True, batch_size=b.batch_size())
         yield q1_loss
         if self.q2_network:
-            q2 = self._e["q2"]
-            yield _SegmentLoss.apply(lambda g: self._critic_backward("q2", g), self._losses["q2"], *q2["params"])
+            yield self._e["q2"].loss(lambda g: self._critic_backward("q2", g), self._losses["q2"])
         # only update the actor after a fixed number of Q updates (:218-222)
         update_actor = batch_idx % self.delayed_policy_update == 0
         self._actor_forward(b, with_loss=update_actor)
         if update_actor:
             self.actor_loss_without_reg = self._losses["plain"]
-            yield _SegmentLoss.apply(self._actor_backward, self._losses["actor"], *self._e["actor"]["params"])
+            yield self._e["actor"].loss(self._actor_backward, self._losses["actor"])
         else:
             self.actor_loss_without_reg = None
             yield None  # None keeps the actor network from updating
         if self._cpe is not None:
-            self._cpe.forward(b)
-            reward_loss = self._cpe.loss("reward")
-            yield reward_loss
-            from .reagent_lightning_module import _NoOpReporter
-
-            if not isinstance(self._reporter, _NoOpReporter):  # dqn_trainer_base.py:430-450 (inside _calculate_cpes)
-                from ..core.torch_utils import masked_softmax
-
-                mask = b.possible_actions_mask if self.maxq_learning else b.action
-                self.reporter.log(reward_loss=reward_loss.detach(),
-                                  model_propensities=masked_softmax(self.all_action_scores, mask.float(), self.rl_temperature),
-                                  model_rewards=self._cpe.reward_est[:, : self.num_actions])
-            yield self._cpe.loss("cpe")
+            # (inside _calculate_cpes: the propensities come from the actor's scores)
+            yield from self._cpe.segment(b, lambda: self.all_action_scores)
         self._log_crr(q1_loss, b)
         yield self.soft_update_result()
 
@@ -306,21 +267,6 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
                           model_action_idxs=self.get_max_q_values(self.all_action_scores, mask.float())[1])
 
     # ---- fused native step -----------------------------------------------------------------------
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            self._native_opts = [o["optimizer"] for o in self.configure_optimizers()]
-        return self._native_opts
-
-    def enable_data_parallel(self, process_group=None):
-        import torch.distributed as dist
-
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        from .dqn_trainer import require_grad_scaling_optimizers
-
-        require_grad_scaling_optimizers(self)  # the 1/world of the summed gradients is folded into the Adam launches
-        return self
-
     @torch.no_grad()
     @native_step
     def train_step_native(self, training_batch, batch_idx: Optional[int] = None):
@@ -329,33 +275,24 @@ class DiscreteCRRTrainer(DQNTrainerBaseLightning):
         b = training_batch
         idx = self._native_idx if batch_idx is None else batch_idx
         self._native_idx = idx + 1
-        gs = 1.0 / self._dp_world
-
-        def step(params, backward):
-            for p in params:
-                p.grad = None
-            backward()
-            o = next(opts)
-            o.grad_scale = gs
-            o.step()
 
         self._critic_forward(b)
         for k in ("q1", "q2"):
             if k in self._e:
-                step(self._e[k]["params"], lambda k=k: self._critic_backward(k))
+                self._native_segment(self._e[k], lambda k=k: self._critic_backward(k), next(opts))
         out = dict(q1_loss=self._losses["q1"], q2_loss=self._losses["q2"] if "q2" in self._e else None,
                    actor_loss=None, reward_loss=None, cpe_loss=None)
         update_actor = idx % self.delayed_policy_update == 0
         self._actor_forward(b, with_loss=update_actor)
         if update_actor:
-            step(self._e["actor"]["params"], self._actor_backward)
+            self._native_segment(self._e["actor"], self._actor_backward, next(opts))
             out["actor_loss"] = self._losses["actor"]
         else:
             next(opts)
         if self._cpe is not None:
             self._cpe.forward(b)
             for k in ("reward", "cpe"):
-                step(self._cpe.e[k]["params"], lambda k=k: self._cpe.backward(k))
+                self._native_segment(self._cpe.e[k], lambda k=k: self._cpe.backward(k), next(opts))
                 out[k + "_loss"] = self._cpe.losses[k]
         next(opts).step()  # soft update of every target
         self.all_batches_processed += 1

@@ -25,6 +25,7 @@ from ..core.parameters import EvaluationParameters, RLParameters
 from ..engine import ensure_slab, grad_views
 from ..optimizer import Optimizer__Union, SoftUpdate
 from .dqn_trainer_base import DQNTrainerBaseLightning
+from .plumbing import NativeStep, NativeStepMixin, SegmentLoss, dp_reduce, held_gradients, publish_gradients
 
 logger = logging.getLogger(__name__)
 
@@ -32,143 +33,6 @@ logger = logging.getLogger(__name__)
 @dataclass(frozen=True)
 class BCQConfig:
     drop_threshold: float = 0.1
-
-
-class _HipLoss(torch.autograd.Function):
-    """Scalar loss whose backward runs the HIP backward pass and writes ``.grad`` in place."""
-
-    @staticmethod
-    def forward(ctx, owner, loss_buf, *params):
-        ctx.owner = owner
-        return loss_buf.detach().clone().reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.owner._hip_backward(grad_out)
-        return (None, None) + (None,) * len(ctx.owner._hip_params)
-
-
-class _SegmentLoss(torch.autograd.Function):
-    """Scalar loss whose backward runs a HIP backward closure (writes ``.grad`` in place)."""
-
-    @staticmethod
-    def forward(ctx, closure, loss_buf, *params):
-        ctx.closure = closure
-        ctx.n = len(params)
-        return loss_buf.detach().clone().reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.closure(grad_out)
-        return (None, None) + (None,) * ctx.n
-
-
-def dp_reduce(tr, slab):
-    """Sum the gradient slab over the data-parallel group (RCCL).  Inside a native step the 1/world factor
-    is folded into the Adam launch (grad_scale); on the generator / Lightning path the optimizers are
-    stepped by the caller, so the sum is turned into the mean here and Adam, weight decay and any gradient
-    clipping see what a single rank would on the concatenated batch."""
-    torch.distributed.all_reduce(slab.grad, group=tr._dp_group)
-    if not getattr(tr, "_native_active", False):
-        slab.grad.mul_(1.0 / tr._dp_world)
-
-
-class _NativeStep:
-    """marks the trainer as inside a native step (see dp_reduce)"""
-
-    def __init__(self, tr):
-        self.tr = tr
-
-    def __enter__(self):
-        self.prev = getattr(self.tr, "_native_active", False)
-        self.tr._native_active = True
-
-    def __exit__(self, *exc):
-        self.tr._native_active = self.prev
-
-
-def held_gradients(slab, params):
-    """A backward without a preceding zero_grad() accumulates in PyTorch, but the HIP backward OVERWRITES
-    the gradient slab.  Returns copies of the gradients still published through p.grad (aliases of the
-    slab) so that `publish_gradients` can add them back; empty when the gradients were cleared
-    (`zero_grad(set_to_none=True)`, every native step)."""
-    base = slab.grad.data_ptr()
-    return [(i, slab.view(slab.grad, i).clone()) for i, p in enumerate(params)
-            if p.grad is not None and p.grad.data_ptr() == base + 4 * slab.offsets[i]]
-
-
-def publish_gradients(slab, params, held=()):
-    """p.grad aliases the slab the backward wrote (gradients held over a missing zero_grad() are added
-    back; foreign .grad tensors are accumulated into)"""
-    for i, g in held:
-        slab.view(slab.grad, i).add_(g)
-    base = slab.grad.data_ptr()
-    for i, p in enumerate(params):
-        gv = slab.view(slab.grad, i)
-        if p.grad is None or p.grad.data_ptr() == base + 4 * slab.offsets[i]:
-            p.grad = gv
-        else:
-            p.grad.add_(gv)
-
-
-def enable_graph_mode(tr):
-    """Switch every Adam of the trainer's native step to device-scheduled stepping (optimizer.AdamSchedule): what
-    a HIP-graph capture of the step needs.  Eager steps keep working (and produce the same bits)."""
-    if any(isinstance(m, torch.nn.Dropout) and m.p > 0.0 for m in tr.modules()):
-        # rg_dropout's Philox offset is a host-side launch argument: a replayed graph would repeat one mask forever
-        raise NotImplementedError("networks with dropout layers are not captured into a HIP graph: run the native step eagerly")
-    for o in tr.native_optimizers():
-        if type(o).__module__.startswith("torch.optim"):
-            # torch's own optimizers (Optimizer__Union's other members) count their steps on the host
-            raise NotImplementedError(f"{type(o).__name__}: only Adam steps are captured into a HIP graph; run the native step eagerly")
-    for o in tr.native_optimizers():
-        if hasattr(o, "enable_device_schedule"):
-            o.enable_device_schedule()
-    tr._graph_mode = True
-
-
-def require_grad_scaling_optimizers(tr):
-    """data parallel on the trainers that fold 1/world into their Adam launches (SAC, TD3, discrete CRR): one of torch's own
-    optimizers (Optimizer__Union's other members) has no such argument — refuse rather than step on summed gradients"""
-    if getattr(tr, "_dp_world", 1) == 1:
-        return
-    for o in tr.native_optimizers():
-        if type(o).__module__.startswith("torch.optim"):  # (this package's own optimizer classes all scale in their launches)
-            raise NotImplementedError(f"{type(tr).__name__}: data parallel needs Adam optimizers (got torch.optim.{type(o).__name__})")
-
-
-def disable_graph_mode(tr):
-    """back to scalar-argument Adam launches (host step counters brought up to date first)"""
-    for o in tr.native_optimizers():
-        if hasattr(o, "disable_device_schedule"):
-            o.disable_device_schedule()
-    tr._graph_mode = False
-
-
-def note_graph_replays(tr, n: int):
-    """host-side bookkeeping for n steps that ran as graph replays (no Python in between)"""
-    if n <= 0:
-        return
-    for o in tr.native_optimizers():
-        if hasattr(o, "note_device_steps"):
-            o.note_device_steps(n)
-        for g in o.param_groups:  # the compute-type weight copies of an eager call after the replays are re-staged
-            for p in g["params"]:
-                p._rg_version = getattr(p, "_rg_version", 0) + 1
-    tr.all_batches_processed += n
-
-
-def native_step(fn):
-    """decorator for train_step_native of the trainers: the whole call runs as a native step"""
-    import functools
-
-    @functools.wraps(fn)
-    def wrapper(self, *a, **k):
-        # (ops.deferred_ticks: the schedule ticks of the step's device-scheduled updates leave as ONE launch at its end)
-        with _NativeStep(self), ops.deferred_ticks():
-            return fn(self, *a, **k)
-
-    return wrapper
 
 
 class _CpeEngine:
@@ -181,16 +45,9 @@ class _CpeEngine:
         self.tr = trainer
         self._ws_batch = -1
 
-    @staticmethod
-    def _net_engine(net):
-        params = list(net.parameters())
-        slab = ensure_slab(params)
-        dw, db = grad_views(net.fc, slab, params)
-        return dict(params=params, slab=slab, stack=net.fc.stack(), dw=dw, db=db)
-
     def _engine(self, B, dev):
         tr = self.tr
-        self.e = dict(reward=self._net_engine(tr.reward_network), cpe=self._net_engine(tr.q_network_cpe))
+        self.e = dict(reward=tr._trainable(tr.reward_network), cpe=tr._trainable(tr.q_network_cpe))
         self.t = tr.q_network_cpe_target.fc.stack()
         if self._ws_batch != B or self.reward_est.device != dev:
             A, M = tr.num_actions, len(tr.metrics_to_score)
@@ -213,9 +70,9 @@ class _CpeEngine:
         # (dqn_trainer.py:268), the target critic's next-state values for CRR
         tr._cpe_next_action_scores(next_state, self.next_scores)
         for k in ("reward", "cpe"):
-            self.e[k]["stack"].stage_weights(need_transposed=True)
+            self.e[k].stack.stage_weights(need_transposed=True)
         self.t.stage_weights(need_transposed=False)
-        rs, cs = self.e["reward"]["stack"], self.e["cpe"]["stack"]
+        rs, cs = self.e["reward"].stack, self.e["cpe"].stack
         xs_r, self._xs_t_r = rs.stage_input(state, need_transposed=True)
         rs.forward(xs_r, self.reward_est, save=True)
         xs_c, self._xs_t_c = cs.stage_input(state, need_transposed=True)
@@ -240,30 +97,37 @@ class _CpeEngine:
             ops.reduce_sum(self.parts[k], self.parts[k].numel(), 1.0 / (B * M), self.losses[k])
 
     def backward(self, which, grad_out=None):
-        e = self.e[which]
-        d = self.d_reward if which == "reward" else self.d_cpe
-        if grad_out is not None:
-            d = d * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(d, self._xs_t_r if which == "reward" else self._xs_t_c, e["dw"], e["db"])
-        slab = e["slab"]
-        if self.tr._dp_group is not None:
-            dp_reduce(self.tr, slab)
-        publish_gradients(slab, e["params"], held)
+        d, xt = (self.d_reward, self._xs_t_r) if which == "reward" else (self.d_cpe, self._xs_t_c)
+        self.e[which].backward(d, xt, grad_out)
 
     def loss(self, which):
-        e = self.e[which]
-        return _SegmentLoss.apply(lambda g: self.backward(which, g), self.losses[which], *e["params"])
+        return self.e[which].loss(lambda g: self.backward(which, g), self.losses[which])
+
+    def segment(self, b, scores):
+        """the two CPE losses of a train_step_gen; `scores()` are the action scores the logged propensities come from"""
+        from .reagent_lightning_module import _NoOpReporter
+
+        tr = self.tr
+        self.forward(b)
+        reward_loss = self.loss("reward")
+        yield reward_loss
+        if not isinstance(tr._reporter, _NoOpReporter):  # dqn_trainer_base.py:430-450
+            from ..core.torch_utils import masked_softmax
+
+            mask = b.possible_actions_mask if tr.maxq_learning else b.action
+            tr.reporter.log(reward_loss=reward_loss.detach(),
+                            model_propensities=masked_softmax(scores(), mask.float(), tr.rl_temperature),
+                            model_rewards=self.reward_est[:, : tr.num_actions])
+        yield self.loss("cpe")
 
 
-class QStepCore(DQNTrainerBaseLightning):
+class QStepCore(NativeStepMixin, DQNTrainerBaseLightning):
     """Engine shared by DQNTrainer and QRDQNTrainer: flat parameter slab, FC stacks, the
     3-forward / head / backward sequence, the autograd bridge and the fused native step.
     Subclasses provide the head (``_alloc_head`` / ``_run_head``) and ``_out_cols``."""
 
     _ws_batch = -1
-    _dp_group = None
-    _dp_world = 1
+    _dp_needs_grad_scaling_optimizers = False  # _step_optimizer scales the gradients of torch's own optimizers itself
 
     def _out_cols(self) -> int:
         return self.num_actions
@@ -287,13 +151,8 @@ class QStepCore(DQNTrainerBaseLightning):
     _cpe = None
 
     def _cpe_gamma_exponent(self, b):
-        """exponent of gamma in the CPE discount tensor (dqn_trainer.py:240-254), None = 1"""
-        gamma_exp = None
-        if self.use_seq_num_diff_as_time_diff:
-            gamma_exp = self._f32c(b.time_diff).reshape(-1)
-        if self.multi_steps is not None:
-            gamma_exp = self._f32c(b.step).reshape(-1)
-        return gamma_exp
+        """exponent of gamma in the CPE discount tensor: the TD head's"""
+        return self._gamma_exponent(b)
 
     def _cpe_next_action_scores(self, next_state, out):
         qs = self._qs
@@ -315,20 +174,7 @@ class QStepCore(DQNTrainerBaseLightning):
         if self._cpe is None:
             self._post_step_stats_forward(training_batch)
             return
-        from .reagent_lightning_module import _NoOpReporter
-
-        self._cpe.forward(training_batch)
-        reward_loss = self._cpe.loss("reward")
-        yield reward_loss
-        if not isinstance(self._reporter, _NoOpReporter):  # dqn_trainer_base.py:430-450
-            from ..core.torch_utils import masked_softmax
-
-            mask = training_batch.possible_actions_mask if self.maxq_learning else training_batch.action
-            self.reporter.log(reward_loss=reward_loss.detach(),
-                              model_propensities=masked_softmax(self._cpe_scores_for_logging(), mask.float(),
-                                                                self.rl_temperature),
-                              model_rewards=self._cpe.reward_est[:, : self.num_actions])
-        yield self._cpe.loss("cpe")
+        yield from self._cpe.segment(training_batch, self._cpe_scores_for_logging)
 
     # ---- engine -------------------------------------------------------------------------------
     def _engine(self, batch: int, device):
@@ -349,11 +195,6 @@ class QStepCore(DQNTrainerBaseLightning):
             self._ws_batch = batch
         # weight/bias gradient destinations = views of the flat gradient slab, in layer order
         self._dw, self._db = grad_views(self.q_network.fc, self._slab, self._hip_params)
-
-    @staticmethod
-    def _f32c(t: torch.Tensor) -> torch.Tensor:
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
 
     def _bcq_mask(self, next_mask, next_state):
         """possible_next_actions_mask * get_valid_actions_from_imitator(imitator, next_state, threshold)
@@ -390,13 +231,6 @@ class QStepCore(DQNTrainerBaseLightning):
         xn, _ = qs.stage_input(self._net_in(training_batch.next_state.float_features), need_transposed=False)
         qs.forward(xn, self._qn_online, save=False)
 
-    @staticmethod
-    def _net_in(t: torch.Tensor) -> torch.Tensor:
-        """network input: fp32, or bf16 (the normalize-on-gather output of the bf16 path)"""
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            t = t.float()
-        return t if t.stride(-1) == 1 and t.is_contiguous() else t.contiguous()
-
     def _hip_forward(self, b) -> torch.Tensor:
         state, next_state = self._net_in(b.state.float_features), self._net_in(b.next_state.float_features)
         L.require_cuda(state, "training_batch.state")
@@ -414,13 +248,7 @@ class QStepCore(DQNTrainerBaseLightning):
         ts.forward(xn, self._qn_target, save=False)
         if not paired:
             qs.forward(xs, self._q, save=True)
-        gamma_exp = None
-        if self.use_seq_num_diff_as_time_diff:
-            assert self.multi_steps is None
-            gamma_exp = self._f32c(b.time_diff).reshape(-1)
-        if self.multi_steps is not None:
-            assert b.step is not None
-            gamma_exp = self._f32c(b.step).reshape(-1)
+        gamma_exp = self._gamma_exponent(b)
         boosts = self.reward_boosts.reshape(-1).to(dev) if self._has_reward_boost else None
         if self.maxq_learning:
             next_mask = self._f32c(b.possible_next_actions_mask)
@@ -464,35 +292,12 @@ class QStepCore(DQNTrainerBaseLightning):
         tail, self._loss_tail = self._loss_tail, None
         return {"tail_sum": tail} if tail is not None else {}
 
-    # ---- data parallel -------------------------------------------------------
-    def enable_data_parallel(self, process_group=None):
-        """All-reduce(sum) the flat fp32 gradient slab over RCCL after every backward; the 1/world
-        factor is folded into the Adam kernel (FusedAdam.grad_scale)."""
-        import torch.distributed as dist
-
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        return self
-
     def _hip_loss(self, batch):
         self.apply_pending_update()  # a deferred native update must land before the next forward
         loss_buf = self._hip_forward(batch)
-        return _HipLoss.apply(self, loss_buf, *self._hip_params)
+        return SegmentLoss.apply(self._hip_backward, loss_buf, *self._hip_params)
 
     # ---- fused native step (what bench.py and the native loop drive) --------------------------
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            made = self.configure_optimizers()
-            self._native_opts = [o["optimizer"] for o in made]
-            # lr schedulers of the optimizer configs (None where there is none): with Lightning its loop
-            # steps them per epoch; a caller of the native loop does `for s in native_schedulers(): s.step()`
-            self._native_scheds = [o.get("lr_scheduler") for o in made]
-        return self._native_opts
-
-    def native_schedulers(self):
-        self.native_optimizers()
-        return [s for s in self._native_scheds if s is not None]
-
     @torch.no_grad()
     def train_step_native(self, training_batch, defer_update: bool = False) -> torch.Tensor:
         """forward + head + backward + Adam + soft update with no autograd graph, no generator and
@@ -512,7 +317,7 @@ class QStepCore(DQNTrainerBaseLightning):
         for p in self._hip_params:
             p.grad = None
         deferred = defer_update and self._dp_group is not None
-        with _NativeStep(self):
+        with NativeStep(self):
             self._hip_backward(None, async_reduce=deferred)
         self._update_pending = True
         self._pending_batch = (training_batch if getattr(self, "_cpe", None) is not None or self._q_has_batch_norm()
@@ -538,7 +343,7 @@ class QStepCore(DQNTrainerBaseLightning):
             self._loss_tail_wanted = False
         for p in self._hip_params:
             p.grad = None
-        with _NativeStep(self):
+        with NativeStep(self):
             self._qs.backward(self._dq, self._xs_t, self._dw, self._db, **self._take_loss_tail())
             publish_gradients(self._slab, self._hip_params)
         return loss
@@ -548,7 +353,7 @@ class QStepCore(DQNTrainerBaseLightning):
         """Adam (1/world folded in) + soft update + re-staging on the gradient slab as it stands"""
         self._update_pending = True
         self._pending_reduce = None
-        with _NativeStep(self):
+        with NativeStep(self):
             self._apply_pending_update()
 
     _update_pending = False
@@ -680,7 +485,7 @@ class QStepCore(DQNTrainerBaseLightning):
         """Adam + soft update of the last backward, after joining its gradient all-reduce."""
         if not self._update_pending:
             return
-        with _NativeStep(self):
+        with NativeStep(self):
             self._apply_pending_update()
 
     def _step_optimizer(self, opt):
@@ -714,8 +519,7 @@ class QStepCore(DQNTrainerBaseLightning):
         if cpe is not None:  # reward network and CPE q-network, in the reference's optimizer order
             cpe.forward(self._pending_batch)
             for which, opt in (("reward", opts[1]), ("cpe", opts[2])):
-                for p in cpe.e[which]["params"]:
-                    p.grad = None
+                cpe.e[which].clear_grads()
                 cpe.backward(which)
                 self._step_optimizer(opt)
         elif self._pending_batch is not None:

@@ -2,7 +2,8 @@
 reagent/training/dqn_trainer_base.py:23-241 for the natively executed trainers.
 
 CPE (reward network / q_network_cpe heads, :243-452) is executed by the
-DQN trainer (`_CpeEngine` in dqn_trainer.py); the trainers that do not run it yet reject
+DQN, QR-DQN and discrete CRR trainers (`_CpeEngine` in dqn_trainer.py, its two networks held as plumbing.TrainableNet;
+`_CpeEngine.segment` is the CPE part of their train_step_gen); the trainers that do not run it yet reject
 calc_cpe_in_training=True at construction rather than silently skipping it.  The Evaluator /
 EvaluationDataPage side (:454-509) is control plane and stays out.
 """

@@ -21,18 +21,16 @@ from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
 from ..core.parameters import RLParameters
-from ..engine import FusedMLP, ensure_slab, grad_views
 from ..optimizer import Optimizer__Union, SoftUpdate
-from .dqn_trainer import dp_reduce, held_gradients, native_step, publish_gradients
 from .dqn_trainer_base import DQNTrainerMixin
+from .plumbing import NativeStepMixin, PanelCriticMixin, native_step
 from .reagent_lightning_module import ReAgentLightningModule
 from .rl_trainer_pytorch import RLTrainerMixin
-from .sac_trainer import _SegmentLoss
 
 _LOSS = dict(L.LOSS, bce_with_logits=L.LOSS_BCE_LOGITS)
 
 
-class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModule):
+class ParametricDQNTrainer(PanelCriticMixin, NativeStepMixin, DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModule):
     def __init__(
         self,
         q_network,
@@ -63,7 +61,6 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
             raise Exception("Q-Network loss type {} not valid loss.".format(rl.q_network_loss))
         self._loss_type = _LOSS[rl.q_network_loss]
         self._ws_key = None
-        self._dp_group, self._dp_world = None, 1
 
     # ---- optimizers (:67-87) -------------------------------------------------------------------------
     def configure_optimizers(self):
@@ -89,22 +86,9 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
         return q_values, q_values_target
 
     # ---- engine --------------------------------------------------------------------------------------
-    @staticmethod
-    def _net_engine(net):
-        params = list(net.parameters())
-        slab = ensure_slab(params)
-        dw, db = grad_views(net.fc, slab, params)
-        return dict(params=params, slab=slab, stack=net.fc.stack(), dw=dw, db=db)
-
-    @staticmethod
-    def _reads_panels(stack, state_dim: int) -> bool:
-        """the fused kernels read cat(state, action) in place as two K-panels (the state panel tiled or not); every other
-        engine, and a state width that is not a multiple of 32, takes the rows rg_tile_concat assembles"""
-        return isinstance(stack, FusedMLP) and state_dim % 32 == 0
-
     def _engine(self, B, M, dev, S, A):
         nets = dict(q=self.q_network, reward=self.reward_network)
-        self._e = {k: self._net_engine(n) for k, n in nets.items() if n is not None}
+        self._e = {k: self._trainable(n) for k, n in nets.items() if n is not None}
         self._t = self.q_network_target.fc.stack()
         key = (B, M, S, A, dev)
         if self._ws_key != key:
@@ -118,43 +102,6 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
             self._losses = {n: torch.empty(1, **f) for n in ("q", "reward")}
             self._cat = {}  # rows -> assembled [rows, S + A] critic input (engines that do not read panels)
             self._ws_key = key
-
-    def _cat_ws(self, rows, S, A, dev):
-        w = self._cat.get(rows)
-        if w is None:
-            w = self._cat[rows] = torch.empty(rows, S + A, dtype=torch.float32, device=dev)
-        return w
-
-    @staticmethod
-    def _f32c(t):
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
-    @staticmethod
-    def _state_in(t, stack):
-        """state rows as a network input: fp32, or network-ready bf16 rows for a fused stack"""
-        if t.dtype == torch.bfloat16 and isinstance(stack, FusedMLP):
-            return t if t.is_contiguous() else t.contiguous()
-        return ParametricDQNTrainer._f32c(t)
-
-    def _critic_rows(self, stack, state, cand, out, M=1, save=False):
-        """out = critic(cat(state[r // M], cand[r])) for every row r of cand; -> the transposed staged input a saving
-        forward of the per-layer engine hands its backward (None on the fused kernels)"""
-        S, A = state.shape[1], cand.shape[1]
-        if self._reads_panels(stack, S):
-            stack.forward(self._state_in(state, stack), out, save=save, x2=cand, x_tile=M)
-            return None
-        x = self._cat_ws(cand.shape[0], S, A, cand.device)
-        ops.tile_concat(self._f32c(state), cand, x, x_tile=M)
-        xc, xt = stack.stage_input(x, need_transposed=save)
-        stack.forward(xc, out, save=save)
-        return xt
-
-    def _publish(self, e, held=()):
-        slab = e["slab"]
-        if self._dp_group is not None:
-            dp_reduce(self, slab)
-        publish_gradients(slab, e["params"], held)
 
     # ---- segments ------------------------------------------------------------------------------------
     def _q_forward(self, b):
@@ -172,23 +119,18 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
             M = product // batch_size
         self._engine(B, M, dev, S, A)
         e, t = self._e["q"], self._t
-        e["stack"].stage_weights(need_transposed=True)
+        e.stack.stage_weights(need_transposed=True)
         t.stage_weights(need_transposed=False)
         if maxq:
             if self.double_q_learning:  # the arg-max keys on the online values (single-q never reads them)
-                self._critic_rows(e["stack"], next_state, pna, self._qn_on, M=M)
+                self._critic_rows(e.stack, next_state, pna, self._qn_on, M=M)
             self._critic_rows(t, next_state, pna, self._qn_tg, M=M)
             qn_tg, mask = self._qn_tg, self._f32c(b.possible_next_actions_mask)
         else:  # SARSA (Use the target network)
             qn_tg, mask = self._qn_tg[:B], None
             self._critic_rows(t, next_state, self._f32c(b.next_action.float_features), qn_tg)
-        gamma_exp = None
-        if self.use_seq_num_diff_as_time_diff:
-            assert self.multi_steps is None
-            gamma_exp = self._f32c(b.time_diff).reshape(-1)
-        if self.multi_steps is not None:
-            gamma_exp = self._f32c(b.step).reshape(-1)
-        self._x_t = self._critic_rows(e["stack"], state, action, self._qv, save=True)  # Q-value of action taken
+        gamma_exp = self._gamma_exponent(b)
+        self._x_t = self._critic_rows(e.stack, state, action, self._qv, save=True)  # Q-value of action taken
         ops.pdqn_head(self._qv, self._qn_on if maxq and self.double_q_learning else None, qn_tg, mask,
                       self._f32c(b.reward).reshape(-1), self._f32c(b.not_terminal).reshape(-1), self.gamma, gamma_exp,
                       self.double_q_learning, self._loss_type, self._y, self._dq, self._parts["q"], self._nq, self._next_idx)
@@ -201,10 +143,10 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
             raise NotImplementedError("ParametricDQNTrainer: a reward_network with training_batch.extras.metrics (a "
                                       "multi-column reward target) is not supported; pass extras.metrics=None")
         e = self._e["reward"]
-        assert e["stack"].dims[-1] == 1, "the reward network has one output column"
-        e["stack"].stage_weights(need_transposed=True)
+        assert e.stack.dims[-1] == 1, "the reward network has one output column"
+        e.stack.stage_weights(need_transposed=True)
         B = b.state.float_features.shape[0]
-        self._xr_t = self._critic_rows(e["stack"], b.state.float_features, self._f32c(b.action.float_features), self._rv,
+        self._xr_t = self._critic_rows(e.stack, b.state.float_features, self._f32c(b.action.float_features), self._rv,
                                        save=True)
         ops.pdqn_head(self._rv, None, self._rv, None, self._f32c(b.reward).reshape(-1),
                       self._f32c(b.not_terminal).reshape(-1), 0.0, None, False, L.LOSS["mse"], self._ry, self._rdq,
@@ -212,25 +154,18 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
         ops.reduce_sum(self._parts["reward"], self._parts["reward"].numel(), 1.0 / B, self._losses["reward"])
 
     def _backward(self, which, grad_out=None):
-        e = self._e[which]
         dq, xt = (self._dq, self._x_t) if which == "q" else (self._rdq, self._xr_t)
-        if grad_out is not None:
-            dq = dq * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dq, xt, e["dw"], e["db"])
-        self._publish(e, held)
+        self._e[which].backward(dq, xt, grad_out)
 
     # ---- reference surface ---------------------------------------------------------------------------
     def train_step_gen(self, training_batch: rlt.ParametricDqnInput, batch_idx: int):
         self._check_input(training_batch)
         b = training_batch
         self._q_forward(b)
-        q = self._e["q"]
-        yield _SegmentLoss.apply(lambda g: self._backward("q", g), self._losses["q"], *q["params"])
+        yield self._e["q"].loss(lambda g: self._backward("q", g), self._losses["q"])
         if self.reward_network is not None:
             self._reward_forward(b)
-            r = self._e["reward"]
-            yield _SegmentLoss.apply(lambda g: self._backward("reward", g), self._losses["reward"], *r["params"])
+            yield self._e["reward"].loss(lambda g: self._backward("reward", g), self._losses["reward"])
             reward_loss = self._losses["reward"].reshape(()).detach().cpu()
         else:
             reward_loss = torch.tensor([0.0])
@@ -241,21 +176,6 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
         yield self.soft_update_result()
 
     # ---- fused native step ---------------------------------------------------------------------------
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            self._native_opts = [o["optimizer"] for o in self.configure_optimizers()]
-        return self._native_opts
-
-    def enable_data_parallel(self, process_group=None):
-        import torch.distributed as dist
-
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        from .dqn_trainer import require_grad_scaling_optimizers
-
-        require_grad_scaling_optimizers(self)  # the 1/world of the summed gradients is folded into the Adam launches
-        return self
-
     @torch.no_grad()
     @native_step
     def train_step_native(self, training_batch):
@@ -263,7 +183,6 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
         graph / generator / host sync; max_num_actions comes from the shapes"""
         opts = self.native_optimizers()
         b = training_batch
-        gs = 1.0 / self._dp_world
         it = iter(opts)
         self._q_forward(b)
         out = dict(td_loss=self._losses["q"], reward_loss=None)
@@ -273,12 +192,7 @@ class ParametricDQNTrainer(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningModu
                     continue
                 self._reward_forward(b)
                 out["reward_loss"] = self._losses["reward"]
-            for p in self._e[which]["params"]:
-                p.grad = None
-            self._backward(which)
-            o = next(it)
-            o.grad_scale = gs
-            o.step()
+            self._native_segment(self._e[which], lambda which=which: self._backward(which), next(it))
         next(it).step()  # soft update
         self.all_batches_processed += 1
         return out

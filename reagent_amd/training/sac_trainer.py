@@ -30,10 +30,10 @@ from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
 from ..core.parameters import RLParameters
-from ..engine import dx_save, ensure_slab, grad_views
+from ..engine import dx_save
 from ..models.actor import LOG_PROB_MAX, LOG_PROB_MIN
 from ..optimizer import Optimizer__Union, SoftUpdate
-from .dqn_trainer import dp_reduce, held_gradients, native_step, publish_gradients
+from .plumbing import NativeStepMixin, SegmentLoss, dp_reduce, held_gradients, native_step
 from .reagent_lightning_module import ReAgentLightningModule
 from .rl_trainer_pytorch import RLTrainerMixin
 
@@ -63,21 +63,6 @@ class CRRWeightFn:
         if self.indicator_fn_threshold:
             return 1, float(self.indicator_fn_threshold), 0.0
         return 2, float(self.exponent_beta), float(self.exponent_clamp or 0.0)
-
-
-class _SegmentLoss(torch.autograd.Function):
-    """Scalar loss whose backward runs a HIP backward closure (writes ``.grad`` in place)."""
-
-    @staticmethod
-    def forward(ctx, closure, loss_buf, *params):
-        ctx.closure = closure
-        ctx.n = len(params)
-        return loss_buf.detach().clone().reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        ctx.closure(grad_out)
-        return (None, None) + (None,) * ctx.n
 
 
 class AdamF64(torch.optim.Optimizer):
@@ -157,7 +142,7 @@ class AdamF64(torch.optim.Optimizer):
         return None
 
 
-class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
+class SACTrainer(NativeStepMixin, RLTrainerMixin, ReAgentLightningModule):
     def __init__(
         self,
         actor_network,
@@ -221,7 +206,6 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         self.use_fused_update = True  # engine.FusedUpdate in the native step
         self._ws_batch = -1
         self._alpha_dev = None
-        self._dp_group, self._dp_world = None, 1
 
     # ---- optimizers (sac_trainer.py:148-193) ---------------------------------------------------
     def configure_optimizers(self):
@@ -269,14 +253,8 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             self._alpha_dev = torch.tensor([val], dtype=torch.float64, device=device)
         return self._alpha_dev
 
-    def _net_engine(self, net):
-        params = list(net.parameters())
-        slab = ensure_slab(params)
-        dw, db = grad_views(net.fc, slab, params)
-        return dict(params=params, slab=slab, stack=net.fc.stack(), dw=dw, db=db)
-
     def _engine(self, B, dev, S, A):
-        self._e = {k: self._net_engine(n) for k, n in dict(actor=self.actor_network, q1=self.q1_network,
+        self._e = {k: self._trainable(n) for k, n in dict(actor=self.actor_network, q1=self.q1_network,
                                                            q2=self.q2_network, value=self.value_network).items()
                    if n is not None}
         self._t = {k: n.fc.stack() for k, n in dict(q1=self.q1_network_target, q2=self.q2_network_target,
@@ -284,13 +262,13 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
                    if n is not None}
         for k in ("q1", "q2"):
             if k in self._e:
-                self._e[k]["stack"].set_need_input_grad(True)
+                self._e[k].stack.set_need_input_grad(True)
         from ..engine import FusedMLP
 
         # cat(state, action) is read in place by the fused kernels as two K-panels (critic.py:79-92) when every
         # critic stack runs on them; the per-layer GEMM engine takes the assembled [B, S + A] matrix
         self._panels = S % 32 == 0 and all(isinstance(st, FusedMLP) for st in
-                                          [self._e[k]["stack"] for k in ("q1", "q2") if k in self._e]
+                                          [self._e[k].stack for k in ("q1", "q2") if k in self._e]
                                           + [st for k, st in self._t.items() if k != "value"])
         if self._ws_batch != B or self._x.device != dev:
             f = dict(dtype=torch.float32, device=dev)
@@ -319,19 +297,6 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             self._alpha_loss = torch.zeros(1, dtype=torch.float64, device=dev)
             self._ws_batch = B
 
-    @staticmethod
-    def _f32c(t):
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
-    @staticmethod
-    def _state_in(t):
-        """state rows as a network input: fp32, or the sampler's network-ready bf16 rows (bf16 engine: the fused
-        kernels would round the fp32 rows to the same bf16 values on load)"""
-        if t.dtype not in (torch.float32, torch.bfloat16):
-            t = t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
     def _actor_out(self, act, x, out, save: bool):
         """actor FC stack -> [loc | scale_log] in `out`; a layer-normed actor passes both halves through their
         LayerNorm (actor.py:194-196), keeping the raw outputs and the statistics of a saving call"""
@@ -345,9 +310,10 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         act.forward(x, raw, save=save)
         return self.actor_network.head_norm(raw, out, self._ln_stats if save else None)
 
-    def _publish(self, e, held=(), reduce=True):
-        slab = e["slab"]
-        if self._dp_group is not None and reduce:
+    def _dp_sum(self, e):
+        """the data-parallel sum of one network's gradient slab (TrainableNet.backward calls it)"""
+        slab = e.slab
+        if self._dp_group is not None:
             rider = self._alpha_rider if e is self._e.get("actor") else None
             if rider is not None:
                 # native data-parallel step: the temperature's gradient rides behind the actor's slab (_dp_actor_bucket) — ONE
@@ -357,7 +323,6 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             else:
                 with ops.profile_span("all_reduce", dict(bytes=slab.grad.numel() * 4, world=self._dp_world)):
                     dp_reduce(self, slab)
-        publish_gradients(slab, e["params"], held)
 
     _alpha_rider = None  # set by the native data-parallel step around the actor's backward pass
 
@@ -367,7 +332,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         is TWO collectives (critics, actor + temperature), not three (few, large collectives).  The fp32 sum over
         the ranks rounds the temperature's gradient at 6e-8 relative; its Adam step is float64 as before."""
         e = self._e["actor"]
-        slab = e["slab"]
+        slab = e.slab
         b = getattr(self, "_dp_bucket_actor", None)
         ok = (b is not None and b.device == slab.grad.device and b.numel() == slab.total + 1
               and slab.grad.data_ptr() == b.data_ptr())
@@ -380,7 +345,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
                 if p.grad is not None and p.grad.data_ptr() == old + 4 * slab.offsets[i]:
                     p.grad = slab.view(view, i)
             slab.grad = view
-            e["dw"], e["db"] = grad_views(self.actor_network.fc, slab, e["params"])
+            e.rebind_grads()
             self._dp_bucket_actor = b
         return b
 
@@ -390,7 +355,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         way, and a step is a chain of them).  Everything that reads a slab's gradients goes through `slab.grad`."""
         if "q2" not in self._e:
             return None
-        s1, s2 = self._e["q1"]["slab"], self._e["q2"]["slab"]
+        s1, s2 = self._e["q1"].slab, self._e["q2"].slab
         b = getattr(self, "_dp_bucket_q", None)
         ok = (b is not None and b.device == s1.grad.device and b.numel() == s1.total + s2.total
               and s1.grad.data_ptr() == b.data_ptr() and s2.grad.data_ptr() == b.data_ptr() + 4 * s1.total)
@@ -405,27 +370,26 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
                         p.grad = slab.view(view, i)
                 slab.grad = view
             for k in ("q1", "q2"):
-                e = self._e[k]
-                e["dw"], e["db"] = grad_views(getattr(self, f"{k}_network").fc, e["slab"], e["params"])
+                self._e[k].rebind_grads()
             self._dp_bucket_q = b
         return b
 
     # ---- segments ----------------------------------------------------------------------------------
     def _critic_forward(self, b, noise_next):
-        state, action = self._state_in(b.state.float_features), self._f32c(b.action.float_features)
-        next_state = self._state_in(b.next_state.float_features)
+        state, action = self._net_in(b.state.float_features), self._f32c(b.action.float_features)
+        next_state = self._net_in(b.next_state.float_features)
         L.require_cuda(state, "training_batch.state")
         B, S, A, dev = state.shape[0], state.shape[1], action.shape[1], state.device
         self._engine(B, dev, S, A)
         self._S, self._A, self._B = S, A, B
         e, t = self._e, self._t
         for k in e:
-            e[k]["stack"].stage_weights(need_transposed=True)
+            e[k].stack.stage_weights(need_transposed=True)
         for k in t:
             t[k].stage_weights(need_transposed=False)
         alpha = self._alpha(dev)
-        act = e["actor"]["stack"]
-        q1s = e["q1"]["stack"]
+        act = e["actor"].stack
+        q1s = e["q1"].stack
         has_q2 = "q2" in e
         if "value" in t:  # next_state_value = value_network_target(next_state), no entropy term (:214-215)
             xn_v, _ = t["value"].stage_input(next_state, need_transposed=False)
@@ -434,14 +398,14 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
                 self._x_t = None
                 q1s.forward(state, self._q1v, save=True, x2=action)
                 if has_q2:
-                    e["q2"]["stack"].forward(state, self._q2v, save=True, x2=action)
+                    e["q2"].stack.forward(state, self._q2v, save=True, x2=action)
             else:
                 self._x[:, :S].copy_(state)
                 self._x[:, S:].copy_(action)
                 x_c, self._x_t = q1s.stage_input(self._x, need_transposed=True)
                 q1s.forward(x_c, self._q1v, save=True)
                 if has_q2:
-                    e["q2"]["stack"].forward(x_c, self._q2v, save=True)
+                    e["q2"].stack.forward(x_c, self._q2v, save=True)
             ops.sac_critic_head(self._q1v, self._q2v if has_q2 else None, self._q1t, None, self._zeros,
                                 self._f32c(b.reward).reshape(-1), self._f32c(b.not_terminal).reshape(-1), self.gamma, alpha,
                                 self._y, self._dq1, self._dq2 if has_q2 else None, self._parts["l1"],
@@ -462,7 +426,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             self._x_t = None
             q1s.forward(state, self._q1v, save=True, x2=action)  # q_i(s, a)
             if has_q2:
-                e["q2"]["stack"].forward(state, self._q2v, save=True, x2=action)
+                e["q2"].stack.forward(state, self._q2v, save=True, x2=action)
         else:
             self._xn[:, :S].copy_(next_state)
             a_next = self._xn[:, S:]
@@ -477,7 +441,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             x_c, self._x_t = q1s.stage_input(self._x, need_transposed=True)
             q1s.forward(x_c, self._q1v, save=True)
             if has_q2:
-                e["q2"]["stack"].forward(x_c, self._q2v, save=True)
+                e["q2"].stack.forward(x_c, self._q2v, save=True)
         ops.sac_critic_head(self._q1v, self._q2v if has_q2 else None, self._q1t, self._q2t if has_q2 else None,
                             self._lpn, self._f32c(b.reward).reshape(-1), self._f32c(b.not_terminal).reshape(-1),
                             self.gamma, alpha, self._y, self._dq1, self._dq2 if has_q2 else None, self._parts["l1"],
@@ -497,7 +461,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
     def _loss_mean(self, key, part, scale, out):
         from ..engine import FusedMLP
 
-        st = self._e[key]["stack"]
+        st = self._e[key].stack
         if self._fold_losses and isinstance(st, FusedMLP) and st.fold_tails and not (key == "actor" and self.add_kld_to_loss):
             self._tails[key] = (part, scale, out)
         else:
@@ -526,43 +490,38 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             m["next_state_value"] = (nsv.reshape(-1) - alpha.float() * lpa.reshape(-1)).mean()
 
     def _critic_backward(self, which, grad_out=None, reduce=True):
-        e = self._e[which]
         dq = self._dq1 if which == "q1" else self._dq2
-        if grad_out is not None:
-            dq = dq * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dq, self._x_t, e["dw"], e["db"], **self._take_tail(which))
-        self._publish(e, held, reduce=reduce)
+        self._e[which].backward(dq, self._x_t, grad_out, reduce=reduce, **self._take_tail(which))
 
     def _actor_forward(self, b, noise_cur):
-        state = self._state_in(b.state.float_features)
+        state = self._net_in(b.state.float_features)
         S, B, dev = self._S, self._B, state.device
         e = self._e
         for k in ("q1", "q2"):  # critics were just updated by their Adam steps
             if k in e:
-                e[k]["stack"].stage_weights(need_transposed=True)
-        act = e["actor"]["stack"]
+                e[k].stack.stage_weights(need_transposed=True)
+        act = e["actor"].stack
         xs_c, self._xs_t = act.stage_input(state, need_transposed=True)
         self._actor_out(act, xs_c, self._ls, save=True)
         self._noise_cur = noise_cur
-        q1s = e["q1"]["stack"]
+        q1s = e["q1"].stack
         has_q2 = "q2" in e
         if self._panels:
             ops.gaussian_head_forward(self._ls, noise_cur, self._api, self._lp, None)
             # the critics are frozen in this segment: only d q / d action comes back (dx_save)
             q1s.forward(state, self._q1a, save=dx_save(q1s), x2=self._api)
             if has_q2:
-                e["q2"]["stack"].forward(state, self._q2a, save=dx_save(q1s), x2=self._api)
+                e["q2"].stack.forward(state, self._q2a, save=dx_save(q1s), x2=self._api)
         else:
             self._xa[:, :S].copy_(state)
             ops.gaussian_head_forward(self._ls, noise_cur, self._xa[:, S:], self._lp, None)
             xa_c, _ = q1s.stage_input(self._xa, need_transposed=False)
             q1s.forward(xa_c, self._q1a, save=dx_save(q1s))
             if has_q2:
-                e["q2"]["stack"].forward(xa_c, self._q2a, save=dx_save(q1s))
+                e["q2"].stack.forward(xa_c, self._q2a, save=dx_save(q1s))
         crr_mode, crr_p0, crr_clamp, v_cur = 0, 0.0, 0.0, None
         if self.crr_config is not None:  # advantage = min q - V(state), both detached (:265-268)
-            vs = e["value"]["stack"]
+            vs = e["value"].stack
             vs.stage_weights(need_transposed=True)
             xv, _ = vs.stage_input(state, need_transposed=False)
             vs.forward(xv, self._vcur, save=False)
@@ -589,33 +548,33 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         e, S = self._e, self._S
         has_q2 = "q2" in e
         if self._panels:  # only the action columns of dQ/d(input) are produced
-            e["q1"]["stack"].backward(self._dq1a, None, None, None, dx32=self._dxa1, skip_wgrad=True, dx_col0=S)
+            e["q1"].stack.backward(self._dq1a, None, None, None, dx32=self._dxa1, skip_wgrad=True, dx_col0=S)
             if has_q2:
-                e["q2"]["stack"].backward(self._dq2a, None, None, None, dx32=self._dxa2, skip_wgrad=True, dx_col0=S)
+                e["q2"].stack.backward(self._dq2a, None, None, None, dx32=self._dxa2, skip_wgrad=True, dx_col0=S)
             ops.add_cols(self._dxa1, self._dxa2 if has_q2 else None, self._ga)
         else:
-            e["q1"]["stack"].backward(self._dq1a, None, None, None, dx32=self._dx1, skip_wgrad=True)
+            e["q1"].stack.backward(self._dq1a, None, None, None, dx32=self._dx1, skip_wgrad=True)
             if has_q2:
-                e["q2"]["stack"].backward(self._dq2a, None, None, None, dx32=self._dx2, skip_wgrad=True)
+                e["q2"].stack.backward(self._dq2a, None, None, None, dx32=self._dx2, skip_wgrad=True)
             ops.add_cols(self._dx1[:, S:], self._dx2[:, S:] if has_q2 else None, self._ga)
         ops.gaussian_head_backward(self._ls, self._noise_cur, self._ga, self._glp.reshape(-1), self._dls,
                                    kld_coef=self._kld_coef if self.add_kld_to_loss else None,
                                    kld_on_mean=self.add_kld_to_loss and self.apply_kld_on_mean)
         dls = self._dls if grad_out is None else self._dls * grad_out
         a = e["actor"]
-        held = held_gradients(a["slab"], a["params"])
+        held = None
         if getattr(self.actor_network, "use_layer_norm", False):  # through loc_layer_norm / scale_layer_norm first
+            held = held_gradients(a.slab, a.params)  # (before the LayerNorms' gradients go into the slab)
             an, A = self.actor_network, self._A
-            index = {id(p): i for i, p in enumerate(a["params"])}
-            view = lambda p: a["slab"].view(a["slab"].grad, index[id(p)])  # noqa: E731
+            index = {id(p): i for i, p in enumerate(a.params)}
+            view = lambda p: a.slab.view(a.slab.grad, index[id(p)])  # noqa: E731
             for h, ln in enumerate((an.loc_layer_norm, an.scale_layer_norm)):
                 sl = slice(h * A, (h + 1) * A)
                 m, r = self._ln_stats[h]
                 ops.layer_norm_backward(dls[:, sl], self._ls_raw[:, sl], m, r, ln.weight.detach(), view(ln.weight),
                                         view(ln.bias), self._ln_ws, dz32=self._dls_raw[:, sl])
             dls = self._dls_raw
-        a["stack"].backward(dls, self._xs_t, a["dw"], a["db"], **self._take_tail("actor"))
-        self._publish(a, held)
+        a.backward(dls, self._xs_t, held=held, **self._take_tail("actor"))
 
     def _alpha_backward(self, grad_out=None, alias=False):
         ops.sac_alpha_grad(self._parts["ent"], self._B, self.log_alpha.data, self._alpha_grad, self._alpha_loss)
@@ -630,8 +589,8 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
     # value segment (:325-340): V(s) regressed on min q (s, a_pi) [- alpha * clamp(log_prob)] — the critic head's
     # arithmetic with reward 0, discount 1, not_terminal 1 and (q1a, q2a) in the place of the target critics
     def _value_forward(self, b):
-        state = self._state_in(b.state.float_features)
-        vs = self._e["value"]["stack"]
+        state = self._net_in(b.state.float_features)
+        vs = self._e["value"].stack
         vs.stage_weights(need_transposed=True)
         xv, self._xv_t = vs.stage_input(state, need_transposed=True)
         vs.forward(xv, self._vval, save=True)
@@ -642,11 +601,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         ops.reduce_sum(self._parts["lv"], self._parts["lv"].numel(), 1.0 / self._B, self._losses["value"])
 
     def _value_backward(self, grad_out=None):
-        e = self._e["value"]
-        dv = self._dv if grad_out is None else self._dv * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dv, self._xv_t, e["dw"], e["db"])
-        self._publish(e, held)
+        self._e["value"].backward(self._dv, self._xv_t, grad_out)
 
     def _noise(self, B, A, dev, given):
         if given is not None:
@@ -668,20 +623,18 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         inj = getattr(self, "_injected", None) or (None, None)
         self._injected = None
         self._critic_forward(b, self._noise(B, A, dev, inj[0]))
-        q1 = self._e["q1"]
-        yield _SegmentLoss.apply(lambda g: self._critic_backward("q1", g), self._losses["q1"], *q1["params"])
+        yield self._e["q1"].loss(lambda g: self._critic_backward("q1", g), self._losses["q1"])
         if self.q2_network:
-            q2 = self._e["q2"]
-            yield _SegmentLoss.apply(lambda g: self._critic_backward("q2", g), self._losses["q2"], *q2["params"])
+            yield self._e["q2"].loss(lambda g: self._critic_backward("q2", g), self._losses["q2"])
         self._actor_forward(b, self._noise(B, A, dev, inj[1]))
-        yield _SegmentLoss.apply(self._actor_backward, self._losses["actor"], *self._e["actor"]["params"])
+        yield self._e["actor"].loss(self._actor_backward, self._losses["actor"])
         if self.alpha_optimizer is not None:
             ops.sac_alpha_grad(self._parts["ent"], self._B, self.log_alpha.data, self._alpha_grad, self._alpha_loss)
-            yield _SegmentLoss.apply(self._alpha_backward, self._alpha_loss, self.log_alpha)
+            yield SegmentLoss.apply(self._alpha_backward, self._alpha_loss, self.log_alpha)
             self.entropy_temperature = self._alpha(dev)  # = exp(log_alpha), written by AdamF64.step (:322)
         if self.value_network is not None:
             self._value_forward(b)
-            yield _SegmentLoss.apply(self._value_backward, self._losses["value"], *self._e["value"]["params"])
+            yield self._e["value"].loss(self._value_backward, self._losses["value"])
         self._log_metrics()
         yield self.soft_update_result()
 
@@ -742,7 +695,7 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
                     if not hasattr(adam, "moments_for"):
                         made = None
                         break
-                    fu = FusedUpdate.make(adam, e[k]["params"], net.fc.linears(), e[k]["stack"],
+                    fu = FusedUpdate.make(adam, e[k].params, net.fc.linears(), e[k].stack,
                                           target_params=list(tgt.parameters()) if tgt is not None else None,
                                           target_stack=self._t[k] if tgt is not None else None, tau=self.tau)
                     if fu is None:
@@ -756,21 +709,6 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             return None
         # (first step: fragments not staged yet -> the separate launches, for every network of the step)
         return plan if all(fu.staged() for fu in plan.values()) else None
-
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            self._native_opts = [o["optimizer"] for o in self.configure_optimizers()]
-        return self._native_opts
-
-    def enable_data_parallel(self, process_group=None):
-        import torch.distributed as dist
-
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        from .dqn_trainer import require_grad_scaling_optimizers
-
-        require_grad_scaling_optimizers(self)  # the 1/world of the summed gradients is folded into the Adam launches
-        return self
 
     @torch.no_grad()
     @native_step
@@ -798,26 +736,18 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
         dp = self._dp_group is not None
         bucket = self._dp_bucket() if dp else None
         critics = [k for k in ("q1", "q2") if k in self._e]
+        fu = fused if fused is not None else {}
         if bucket is not None:
             # data parallel, twin critics: both backward passes first (q2's reads nothing q1's update writes), ONE all-reduce
             # of the two slabs, then the two updates in the reference's order
             for k in critics:
-                for p in self._e[k]["params"]:
-                    p.grad = None
+                self._e[k].clear_grads()
                 self._critic_backward(k, reduce=False)
             with ops.profile_span("all_reduce", dict(bytes=bucket.numel() * 4, world=self._dp_world)):
                 torch.distributed.all_reduce(bucket, group=self._dp_group)
         for k in critics:
-            if bucket is None:
-                for p in self._e[k]["params"]:
-                    p.grad = None
-                self._critic_backward(k)
-            o = next(it)
-            if fused is not None:
-                fused[k].step(gs)
-            else:
-                o.grad_scale = gs
-                o.step()
+            backward = (lambda k=k: self._critic_backward(k)) if bucket is None else None
+            self._native_segment(self._e[k], backward, next(it), fu.get(k))
         self._actor_forward(b, self._noise(B, A, dev, noise_cur))
         alpha_reduce = None
         if self.alpha_optimizer is not None and dp:
@@ -828,44 +758,31 @@ class SACTrainer(RLTrainerMixin, ReAgentLightningModule):
             self._alpha_backward(alias=True)
             alpha_reduce = self._dp_actor_bucket()
             alpha_reduce[-1:].copy_(self.log_alpha.grad)
-        for p in self._e["actor"]["params"]:
-            p.grad = None
-        self._alpha_rider = alpha_reduce
-        try:
-            self._actor_backward()
-        finally:
-            self._alpha_rider = None
-        o = next(it)
-        alpha_opt = next(it) if self.alpha_optimizer is not None else None
 
-        def actor_and_temperature():
-            if fused is not None:
-                fused["actor"].step(gs)
+        def actor_backward():
+            self._alpha_rider = alpha_reduce
+            try:
+                self._actor_backward()
+            finally:
+                self._alpha_rider = None
+
+        self._native_segment(self._e["actor"], actor_backward, next(it), fu.get("actor"))
+        if self.alpha_optimizer is not None:
+            alpha_opt = next(it)
+            if alpha_reduce is not None:
+                self.log_alpha.grad.copy_(alpha_reduce[-1:])  # the sum over the ranks (float64 again for its Adam step)
+                self.log_alpha.grad.mul_(gs)
             else:
-                o.grad_scale = gs
-                o.step()
-            if alpha_opt is not None:
-                if alpha_reduce is not None:
-                    self.log_alpha.grad.copy_(alpha_reduce[-1:])  # the sum over the ranks (float64 again for its Adam step)
-                    self.log_alpha.grad.mul_(gs)
-                else:
-                    self.log_alpha.grad = None
-                    self._alpha_backward(alias=True)
-                alpha_opt.step()
-                # the aliased gradient IS the kernel's output buffer: never leave it attached — a later generator-path backward
-                # with grads kept (zero_grad(set_to_none=False)) would add the buffer to itself after the kernel rewrote it
                 self.log_alpha.grad = None
-                self.entropy_temperature = self._alpha(dev)
-
-        actor_and_temperature()
+                self._alpha_backward(alias=True)
+            alpha_opt.step()
+            # the aliased gradient IS the kernel's output buffer: never leave it attached — a later generator-path backward
+            # with grads kept (zero_grad(set_to_none=False)) would add the buffer to itself after the kernel rewrote it
+            self.log_alpha.grad = None
+            self.entropy_temperature = self._alpha(dev)
         if self.value_network is not None:
             self._value_forward(b)
-            for p in self._e["value"]["params"]:
-                p.grad = None
-            self._value_backward()
-            o = next(it)
-            o.grad_scale = gs
-            o.step()
+            self._native_segment(self._e["value"], self._value_backward, next(it))
         soft = next(it)
         if fused is None:
             soft.step()  # (the fused critic updates already moved their targets)

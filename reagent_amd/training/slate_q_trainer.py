@@ -25,11 +25,9 @@ from .. import ops
 from ..core import parameters as rlp
 from ..core import types as rlt
 from ..optimizer import Optimizer__Union, SoftUpdate
-from .dqn_trainer import held_gradients, native_step, publish_gradients
-from .parametric_dqn_trainer import ParametricDQNTrainer as _Parametric
+from .plumbing import NativeStepMixin, PanelCriticMixin, native_step
 from .reagent_lightning_module import ReAgentLightningModule
 from .rl_trainer_pytorch import RLTrainerMixin
-from .sac_trainer import _SegmentLoss
 
 
 class NextSlateValueNormMethod(enum.Enum):
@@ -40,7 +38,7 @@ class NextSlateValueNormMethod(enum.Enum):
     NORM_BY_NEXT_SLATE_SIZE = "norm_by_next_slate_size"
 
 
-class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
+class SlateQTrainer(PanelCriticMixin, NativeStepMixin, RLTrainerMixin, ReAgentLightningModule):
     def __init__(
         self,
         q_network,
@@ -76,27 +74,9 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         optimizers.append(SoftUpdate.make_optimizer_scheduler(target_params, source_params, tau=self.tau))
         return optimizers
 
-    # ---- engine (shared with the parametric trainer: the same critic on the same kind of rows) ----------------------
-    _net_engine = staticmethod(_Parametric._net_engine)
-    _reads_panels = staticmethod(_Parametric._reads_panels)
-    _f32c = staticmethod(_Parametric._f32c)
-    _state_in = staticmethod(_Parametric._state_in)
-    _cat_ws = _Parametric._cat_ws
-    _panel_rows = _Parametric._critic_rows
-
-    def _critic_rows(self, stack, state, cand, out, M=1, save=False):
-        """_Parametric._critic_rows, except that a SAVING forward on tiled rows always takes assembled rows: the fused
-        kernels' tiled two-panel forward saves nothing for a backward"""
-        if not (save and M > 1):
-            return self._panel_rows(stack, state, cand, out, M=M, save=save)
-        x = self._cat_ws(cand.shape[0], state.shape[1], cand.shape[1], cand.device)
-        ops.tile_concat(self._f32c(state), cand, x, x_tile=M)
-        xc, xt = stack.stage_input(x, need_transposed=True)
-        stack.forward(xc, out, save=True)
-        return xt
-
+    # ---- engine (PanelCriticMixin: the parametric trainer's critic on the same kind of rows) ------------------------
     def _engine(self, B, C, K, S, D, dev):
-        self._e = self._net_engine(self.q_network)
+        self._e = self._trainable(self.q_network)
         self._t = self.q_network_target.fc.stack()
         key = (B, C, K, S, D, dev)
         if self._ws_key != key:
@@ -148,7 +128,7 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         not_terminal = self._f32c(b.not_terminal).reshape(-1)
         self._engine(B, C, K, S, D, dev)
         e, t = self._e, self._t
-        e["stack"].stage_weights(need_transposed=True)
+        e.stack.stage_weights(need_transposed=True)
         t.stage_weights(need_transposed=False)
         if maxq:
             assert 0 < self.slate_size <= C
@@ -164,7 +144,7 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         # Get Q-value of action taken
         ops.slate_gather(feats, mask, value, action, self._panel, self._w, count_mask=reward_mask if single else None,
                          count_out=self._n if single else None)
-        self._x_t = self._critic_rows(e["stack"], state, self._panel, self._qv, M=K, save=True)
+        self._x_t = self._critic_rows(e.stack, state, self._panel, self._qv, M=K, save=True)
         # Adjust the discount factor by the time_diff if the discount_time_scale is provided (:211-214)
         time_diff = None
         if self.discount_time_scale and b.time_diff is not None:
@@ -176,18 +156,12 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         return B, K, reward_mask
 
     def _backward(self, grad_out=None):
-        e = self._e
-        dq = self._dq.view(-1, 1)
-        if grad_out is not None:
-            dq = dq * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dq, self._x_t, e["dw"], e["db"])
-        publish_gradients(e["slab"], e["params"], held)
+        self._e.backward(self._dq.view(-1, 1), self._x_t, grad_out)
 
     # ---- reference surface ---------------------------------------------------------------------------
     def train_step_gen(self, training_batch: rlt.SlateQInput, batch_idx: int):
         B, K, reward_mask = self._q_forward(training_batch)
-        yield _SegmentLoss.apply(lambda g: self._backward(g), self._loss, *self._e["params"])
+        yield self._e.loss(self._backward, self._loss)
         q_values = self._qv.detach().view(B, K).cpu()
         if self.single_selection:
             all_action_scores = q_values[reward_mask.cpu()]  # (the reporter is fed on the host: a data-dependent shape)
@@ -199,11 +173,6 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         yield self.soft_update_result()
 
     # ---- fused native step ---------------------------------------------------------------------------
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            self._native_opts = [o["optimizer"] for o in self.configure_optimizers()]
-        return self._native_opts
-
     def enable_data_parallel(self, process_group=None):
         raise NotImplementedError("SlateQTrainer has no data-parallel path: the single-selection loss is a mean over the "
                                   "GLOBAL number of observed rewards, which the ranks would have to agree on")
@@ -215,11 +184,7 @@ class SlateQTrainer(RLTrainerMixin, ReAgentLightningModule):
         rewards stays on the device)"""
         q_opt, soft = self.native_optimizers()
         self._q_forward(training_batch)
-        for p in self._e["params"]:
-            p.grad = None
-        self._backward()
-        q_opt.grad_scale = 1.0
-        q_opt.step()
+        self._native_segment(self._e, self._backward, q_opt)
         soft.step()
         self.all_batches_processed += 1
         return dict(td_loss=self._loss)

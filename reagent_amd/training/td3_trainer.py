@@ -16,17 +16,16 @@ from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
 from ..core.parameters import RLParameters
-from ..engine import dx_save, ensure_slab, grad_views
+from ..engine import dx_save
 from ..optimizer import Optimizer__Union, SoftUpdate
 from .reagent_lightning_module import ReAgentLightningModule
 from .rl_trainer_pytorch import RLTrainerMixin
-from .dqn_trainer import dp_reduce, held_gradients, native_step, publish_gradients
-from .sac_trainer import _SegmentLoss
+from .plumbing import NativeStepMixin, native_step
 
 CONTINUOUS_TRAINING_ACTION_RANGE = (-1.0, 1.0)  # reagent/core/parameters.py:20
 
 
-class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
+class TD3Trainer(NativeStepMixin, RLTrainerMixin, ReAgentLightningModule):
     def __init__(
         self,
         actor_network,
@@ -59,7 +58,6 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
         self.noise_clip_range = (-noise_clip, noise_clip)
         self.delayed_policy_update = delayed_policy_update
         self._ws_batch = -1
-        self._dp_group, self._dp_world = None, 1
         self._native_idx = 0
 
     # ---- optimizers (td3_trainer.py:89-122) ------------------------------------------------------
@@ -79,20 +77,13 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
         return optimizers
 
     # ---- engine ----------------------------------------------------------------------------------
-    @staticmethod
-    def _net_engine(net):
-        params = list(net.parameters())
-        slab = ensure_slab(params)
-        dw, db = grad_views(net.fc, slab, params)
-        return dict(params=params, slab=slab, stack=net.fc.stack(), dw=dw, db=db)
-
     def _engine(self, B, dev, S, A):
         nets = dict(actor=self.actor_network, q1=self.q1_network, q2=self.q2_network)
-        self._e = {k: self._net_engine(n) for k, n in nets.items() if n is not None}
+        self._e = {k: self._trainable(n) for k, n in nets.items() if n is not None}
         tg = dict(actor=self.actor_network_target, q1=self.q1_network_target,
                   q2=getattr(self, "q2_network_target", None))
         self._t = {k: n.fc.stack() for k, n in tg.items() if n is not None}
-        self._e["q1"]["stack"].set_need_input_grad(True)
+        self._e["q1"].stack.set_need_input_grad(True)
         if self._ws_batch != B or self._x.device != dev:
             f = dict(dtype=torch.float32, device=dev)
             P = ops.sac_partials(B)
@@ -108,17 +99,6 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
             self._losses = {n: torch.empty(1, **f) for n in ("q1", "q2", "actor")}
             self._ws_batch = B
 
-    @staticmethod
-    def _f32c(t):
-        t = t if t.dtype == torch.float32 else t.float()
-        return t if t.is_contiguous() else t.contiguous()
-
-    def _publish(self, e, held=()):
-        slab = e["slab"]
-        if self._dp_group is not None:
-            dp_reduce(self, slab)
-        publish_gradients(slab, e["params"], held)
-
     # ---- segments --------------------------------------------------------------------------------
     def _critic_forward(self, b, noise):
         state, action = self._f32c(b.state.float_features), self._f32c(b.action.float_features)
@@ -130,7 +110,7 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
         e, t = self._e, self._t
         for k in ("q1", "q2"):
             if k in e:
-                e[k]["stack"].stage_weights(need_transposed=True)
+                e[k].stack.stage_weights(need_transposed=True)
         for k in t:
             t[k].stage_weights(need_transposed=False)
         # a' = clamp(actor_target(s') + clamp(noise * variance, +-clip), training range)  (:141-146)
@@ -150,11 +130,11 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
             t["q2"].forward(xn_c, self._q2t, save=False)
         self._x[:, :S].copy_(state)
         self._x[:, S:].copy_(action)
-        q1s = e["q1"]["stack"]
+        q1s = e["q1"].stack
         x_c, self._x_t = q1s.stage_input(self._x, need_transposed=True)
         q1s.forward(x_c, self._q1v, save=True)
         if has_q2:
-            e["q2"]["stack"].forward(x_c, self._q2v, save=True)
+            e["q2"].stack.forward(x_c, self._q2v, save=True)
         # y = r + gamma * not_terminal * min(q1', q2'); mse for both critics (:147-167) — the SAC
         # critic head with temperature 0
         ops.sac_critic_head(self._q1v, self._q2v if has_q2 else None, self._q1t, self._q2t if has_q2 else None,
@@ -167,20 +147,14 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
             ops.reduce_sum(self._parts["l2"], P, 1.0 / B, self._losses["q2"])
 
     def _critic_backward(self, which, grad_out=None):
-        e = self._e[which]
-        dq = self._dq1 if which == "q1" else self._dq2
-        if grad_out is not None:
-            dq = dq * grad_out
-        held = held_gradients(e["slab"], e["params"])
-        e["stack"].backward(dq, self._x_t, e["dw"], e["db"])
-        self._publish(e, held)
+        self._e[which].backward(self._dq1 if which == "q1" else self._dq2, self._x_t, grad_out)
 
     def _actor_forward(self, b):
         state = self._f32c(b.state.float_features)
         S, B = self._S, self._B
         e = self._e
-        e["q1"]["stack"].stage_weights(need_transposed=True)  # q1 was just updated by its Adam step
-        act = e["actor"]["stack"]
+        e["q1"].stack.stage_weights(need_transposed=True)  # q1 was just updated by its Adam step
+        act = e["actor"].stack
         act.stage_weights(need_transposed=True)
         xs_c, self._xs_t = act.stage_input(state, need_transposed=True)
         act.forward(xs_c, self._a_out, save=True)
@@ -191,7 +165,7 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
             self._xa[:, S:].copy_(noisy)
         else:
             self._xa[:, S:].copy_(self._a_out)
-        q1s = e["q1"]["stack"]
+        q1s = e["q1"].stack
         xa_c, _ = q1s.stage_input(self._xa, need_transposed=False)
         q1s.forward(xa_c, self._q1a, save=dx_save(q1s))  # q1 is frozen here: only d q / d action comes back
         ops.reduce_sum(self._q1a.reshape(-1), B, -1.0 / B, self._losses["actor"])  # -(q1(s, actor(s)).mean())
@@ -199,14 +173,11 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
     def _actor_backward(self, grad_out=None):
         e, S = self._e, self._S
         dq = self._dq1a if grad_out is None else self._dq1a * grad_out
-        e["q1"]["stack"].backward(dq, None, None, None, dx32=self._dx1, skip_wgrad=True)
-        a = e["actor"]
+        e["q1"].stack.backward(dq, None, None, None, dx32=self._dx1, skip_wgrad=True)
         da = self._dx1[:, S:]
         if self._clamp_passes is not None:  # backward of the exploration clamp
             da = da * self._clamp_passes
-        held = held_gradients(a["slab"], a["params"])
-        a["stack"].backward(da, self._xs_t, a["dw"], a["db"], out32=self._a_out)
-        self._publish(a, held)
+        e["actor"].backward(da, self._xs_t, out32=self._a_out)
 
     def _noise(self, B, A, dev, given):
         if given is not None:
@@ -237,41 +208,24 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
             next_q = torch.minimum(self._q1t, self._q2t) if has_q2 else self._q1t
             self.reporter.log(q1_loss=self._losses["q1"].reshape(()).clone(), q1_value=self._q1v.reshape(-1, 1).clone(),
                               next_q_value=next_q.reshape(-1, 1), target_q_value=self._y.reshape(-1, 1).clone())
-        q1 = self._e["q1"]
-        yield _SegmentLoss.apply(lambda g: self._critic_backward("q1", g), self._losses["q1"], *q1["params"])
+        yield self._e["q1"].loss(lambda g: self._critic_backward("q1", g), self._losses["q1"])
         if self.q2_network:
             if report:
                 self.reporter.log(q2_loss=self._losses["q2"].reshape(()).clone(), q2_value=self._q2v.reshape(-1, 1).clone())
-            q2 = self._e["q2"]
-            yield _SegmentLoss.apply(lambda g: self._critic_backward("q2", g), self._losses["q2"], *q2["params"])
+            yield self._e["q2"].loss(lambda g: self._critic_backward("q2", g), self._losses["q2"])
         # only update actor and target networks after a fixed number of Q updates (:176-199)
         if batch_idx % self.delayed_policy_update == 0:
             self._actor_forward(b)
             if report:
                 self.reporter.log(actor_loss=self._losses["actor"].reshape(()).clone(),
                                   actor_q1_value=self._q1a.reshape(-1, 1).clone())
-            yield _SegmentLoss.apply(self._actor_backward, self._losses["actor"], *self._e["actor"]["params"])
+            yield self._e["actor"].loss(self._actor_backward, self._losses["actor"])
             yield self.soft_update_result()
         else:
             yield None  # None keeps the actor and the target networks from updating
             yield None
 
     # ---- fused native step -----------------------------------------------------------------------
-    def native_optimizers(self):
-        if getattr(self, "_native_opts", None) is None:
-            self._native_opts = [o["optimizer"] for o in self.configure_optimizers()]
-        return self._native_opts
-
-    def enable_data_parallel(self, process_group=None):
-        import torch.distributed as dist
-
-        self._dp_group = process_group if process_group is not None else dist.group.WORLD
-        self._dp_world = dist.get_world_size(self._dp_group)
-        from .dqn_trainer import require_grad_scaling_optimizers
-
-        require_grad_scaling_optimizers(self)  # the 1/world of the summed gradients is folded into the Adam launches
-        return self
-
     @torch.no_grad()
     @native_step
     def train_step_native(self, training_batch, noise=None, batch_idx: Optional[int] = None):
@@ -282,27 +236,17 @@ class TD3Trainer(RLTrainerMixin, ReAgentLightningModule):
         B, A = b.action.float_features.shape
         idx = self._native_idx if batch_idx is None else batch_idx
         self._native_idx = idx + 1
-        gs = 1.0 / self._dp_world
         it = iter(opts)
         self._critic_forward(b, self._noise(B, A, b.action.float_features.device, noise))
         for k in ("q1", "q2"):
             if k in self._e:
-                for p in self._e[k]["params"]:
-                    p.grad = None
-                self._critic_backward(k)
-                o = next(it)
-                o.grad_scale = gs
-                o.step()
+                self._native_segment(self._e[k], lambda k=k: self._critic_backward(k), next(it))
         actor_opt, soft = next(it), next(it)
         out = dict(q1_loss=self._losses["q1"], q2_loss=self._losses["q2"] if "q2" in self._e else None,
                    actor_loss=None)
         if idx % self.delayed_policy_update == 0:
             self._actor_forward(b)
-            for p in self._e["actor"]["params"]:
-                p.grad = None
-            self._actor_backward()
-            actor_opt.grad_scale = gs
-            actor_opt.step()
+            self._native_segment(self._e["actor"], self._actor_backward, actor_opt)
             soft.step()
             out["actor_loss"] = self._losses["actor"]
         self.all_batches_processed += 1

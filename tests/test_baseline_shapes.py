@@ -306,7 +306,7 @@ def test_c4_sac_matches_reference(mode):
               f"rel dloss { {k: float('%.2e' % v) for k, v in dl.items()} } max|dW| { {k: float('%.2e' % v) for k, v in dw.items()} } "
               f"|dlog_alpha| {d_alpha:.2e}")
         actor_frac = max(frac_beyond(p, g, f"step{s}_actor_{i}") for i, p in enumerate(tr.actor_network.parameters()))
-        dg = {n: grad_err(tr._e[n]["slab"].grad_views(), g, f"step{s}_grad_{n}_") for n in ("q1", "q2", "actor")}
+        dg = {n: grad_err(tr._e[n].slab.grad_views(), g, f"step{s}_grad_{n}_") for n in ("q1", "q2", "actor")}
         print(f"  max|dg|/max|g| { {k: float('%.2e' % v) for k, v in dg.items()} }; actor weights beyond 2e-5: "
               f"{100 * actor_frac:.2f} % of the sampled elements (worst tensor)")
         if mode in ACCURATE and s == 0:

@@ -162,11 +162,11 @@ def _worker(rank, world, port, kind, out_dir):
         # as one float behind the actor's slab: TWO collectives per step (rounds 4-5: three; the reference's DDP would take
         # one per parameter bucket)
         n_steps = 3 if fused else 2
-        s1, s2 = tr._e["q1"]["slab"], tr._e["q2"]["slab"]
+        s1, s2 = tr._e["q1"].slab, tr._e["q2"].slab
         assert tr._dp_bucket_q.numel() == s1.total + s2.total and s1.grad.data_ptr() == tr._dp_bucket_q.data_ptr()
         assert s2.grad.data_ptr() == tr._dp_bucket_q.data_ptr() + 4 * s1.total
         per_step = calls[:len(calls) // n_steps]
-        sa = tr._e["actor"]["slab"]
+        sa = tr._e["actor"].slab
         assert len(calls) == 2 * n_steps and per_step[0] == (s1.total + s2.total, False), calls
         assert per_step[1] == (sa.total + 1, False) and sa.grad.data_ptr() == tr._dp_bucket_actor.data_ptr(), calls
     if kind == "qr_fused":
@@ -176,7 +176,7 @@ def _worker(rank, world, port, kind, out_dir):
     elif fused:
         from reagent_amd.engine import FusedMLP
 
-        st = tr._qs if kind.startswith("dqn") else tr._e["q1"]["stack"]
+        st = tr._qs if kind.startswith("dqn") else tr._e["q1"].stack
         assert isinstance(st, FusedMLP) and tr._fused_plan not in (None, False) and st.x3 == (kind == "dqn_x3")
     if kind == "dqn_deferred":
         assert tr._update_pending  # the last update is still waiting for its all-reduce

@@ -426,7 +426,7 @@ def test_dropout_networks_refuse_graph_capture(backend):
     from reagent_amd.models import FullyConnectedDQN
     from reagent_amd.optimizer import Optimizer__Union
     from reagent_amd.training import DQNTrainer
-    from reagent_amd.training.dqn_trainer import enable_graph_mode
+    from reagent_amd.training.plumbing import enable_graph_mode
 
     q = FullyConnectedDQN(6, 3, [16, 16], ["relu", "relu"], dropout_ratio=0.2).to(backend.device)
     tr = DQNTrainer(q, q.get_target_network(), None, actions=["a", "b", "c"], rl=RLParameters(),

@@ -494,7 +494,7 @@ def _device_state(args, trainer):
     opts = trainer.native_optimizers()
     if args.algo == "sac":
         nets = dict(q1=trainer.q1_network, q2=trainer.q2_network, actor=trainer.actor_network)
-        grads = {n: _clone(trainer._e[n]["slab"].grad_views()) for n in ("q1", "q2", "actor")}
+        grads = {n: _clone(trainer._e[n].slab.grad_views()) for n in ("q1", "q2", "actor")}
         moments = {n: [(opts[i].state[p]["exp_avg"].clone(), opts[i].state[p]["exp_avg_sq"].clone()) for p in nets[n].parameters()]
                    for i, n in enumerate(("q1", "q2", "actor"))}
         st = opts[3].state[trainer.log_alpha]

@@ -84,7 +84,7 @@ def _dqn(dev, S=12, A=4, hidden=(32, 16)):
 def test_dqn_and_sac_steps_in_graph_mode_equal_plain_steps(backend):
     """enable_graph_mode changes where the coefficients come from, not the result (eager steps on both sides)"""
     from reagent_amd.training import SACTrainer
-    from reagent_amd.training.dqn_trainer import enable_graph_mode, note_graph_replays
+    from reagent_amd.training.plumbing import enable_graph_mode, note_graph_replays
 
     dev = backend.device
     a, b = _dqn(dev), _dqn(dev)
@@ -327,7 +327,7 @@ def test_data_parallel_three_graph_replay_on_a_one_rank_rccl_group():
 
 
 def test_leaving_graph_mode_keeps_the_step_count(emu_lib):
-    from reagent_amd.training.dqn_trainer import disable_graph_mode, enable_graph_mode
+    from reagent_amd.training.plumbing import disable_graph_mode, enable_graph_mode
 
     a, b = _dqn("cpu"), _dqn("cpu")
     enable_graph_mode(b)
@@ -353,7 +353,7 @@ def test_replayed_step_protocol_on_the_interpreter(emu_lib):
     from reagent_amd.replay_memory import ReplayBuffer
     from reagent_amd.runtime import OfflineDqnLoop
     from reagent_amd.training import DQNTrainer
-    from reagent_amd.training.dqn_trainer import enable_graph_mode
+    from reagent_amd.training.plumbing import enable_graph_mode
 
     S, A, C, B, P = 24, 4, 512, 64, 3
 

@@ -245,7 +245,7 @@ def test_fused_network_updates_equal_the_separate_launches(backend, monkeypatch)
                        (ta.q1_network_target, tb.q1_network_target)):
             for pa, pb in zip(na.parameters(), nb.parameters()):
                 assert torch.equal(pa.detach().cpu(), pb.detach().cpu()), s
-    assert isinstance(ta._e["q1"]["stack"], FusedMLP) and ta._fused_plan and tb._fused_plan is False
+    assert isinstance(ta._e["q1"].stack, FusedMLP) and ta._fused_plan and tb._fused_plan is False
     launches = []
     from reagent_amd import ops
     real = ops._run
@@ -296,7 +296,7 @@ def test_bf16_state_rows_from_the_sampler_equal_fp32_rows(backend):
         return OfflinePolicyLoop(rb, tr, B, maker, pre, state_dtype=state_dtype), tr
 
     (la, ta), (lb, tb) = build(torch.bfloat16), build(None)
-    assert isinstance(ta._e["q1"]["stack"] if hasattr(ta, "_e") else ta.q1_network.fc.stack(), FusedMLP)
+    assert isinstance(ta._e["q1"].stack if hasattr(ta, "_e") else ta.q1_network.fc.stack(), FusedMLP)
     g = torch.Generator().manual_seed(9)
     for s in range(3):
         idx = torch.randint(C, (B,), generator=g)
@@ -347,7 +347,7 @@ def test_device_scheduled_step_ticks_its_schedules_in_one_launch(backend, monkey
     (graph mode).  Their ticks leave as ONE rg_sched_tick_many launch at the end of the native step (ops.deferred_ticks) — and the
     scheduled steps stay bit-identical to the scalar-coefficient steps."""
     from reagent_amd import ops
-    from reagent_amd.training.dqn_trainer import enable_graph_mode
+    from reagent_amd.training.plumbing import enable_graph_mode
 
     g = Golden("sac_twin")
     res = {}
