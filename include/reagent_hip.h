@@ -653,6 +653,48 @@ int rg_slateq_head(const float* q, const float* qn, const float* wn, const float
                    const int32_t* n_selected, int batch, int num_items, float* target, float* dq, float* loss_partials,
                    float* next_q, rg_stream_t stream);
 
+/* ABI 15 — policy gradient (reagent/training/reinforce_trainer.py, reagent/training/ppo_trainer.py) on PACKED
+ * trajectories: N rows, trajectory t the rows [offsets[t], offsets[t + 1]), offsets [T + 1] int32 in DEVICE memory,
+ * ascending, offsets[T] = N.
+ * rg_pg_returns: per trajectory discounted_returns(clamp(reward, max = reward_clip), gamma)
+ * (reagent/training/utils.py:42-54, reinforce_trainer.py:106-108, ppo_trainer.py:225-227) — run = reward[t] + gamma * run
+ * from the trajectory's end, gamma rounded to fp32, multiply and add rounded separately: the reference's bits; gamma == 0
+ * is the copy the reference makes.  Then normalize != 0: whiten(x, subtract_mean) (utils.py:32-39: the population
+ * standard deviation + EPS, EPS = float64's epsilon added in fp32); normalize == 0 and subtract_mean != 0: x - x.mean()
+ * (reinforce_trainer.py:113-114).  Then clamp_min != 0: clamp(min = 0) (:115-116).  Mean and variance are summed in
+ * double.  A wave per trajectory; an empty trajectory writes nothing; rows outside [offsets[0], offsets[T]) are not
+ * written; offsets outside [0, N] are clamped into it.  RG_EINVAL for T < 1 or N < 0.
+ * rg_pg_head: one launch over N rows.  scores [N, A] fp32 (row pitch ld_scores) = the scorer's output;
+ * possible_actions_mask (nullable, [N, A] fp32 contiguous): scores + (1 - mask) * -1e10 is formed first as
+ * FullyConnectedDQN.forward does (reagent/models/dqn.py:60-62) — NULL where the scores already carry it.  action [N, A]
+ * (pitch ld_action, in elements) a one-hot in fp32 or int64 (action_is_int64): its first arg-max is the logged action a
+ * (reagent/gym/policies/samplers/discrete_sampler.py:67-71).  z = scores / temperature, logp = z - logsumexp(z),
+ * p = softmax(z), l = logp[a], H = -sum p * logp (terms with p = 0 count 0), adv = returns - values (values NULL: returns).
+ *   RG_PG_REINFORCE (reinforce_trainer.py:105,132)       loss = -adv * l                      g = -adv
+ *   RG_PG_REINFORCE_OFF_POLICY (:124-130), clip = clip_param, d = l - old_log_prob, e = exp(min(d, log clip)):
+ *                                                          loss = -adv * e                      g = d <= log clip ? -adv * e : 0
+ *   RG_PG_PPO (ppo_trainer.py:127-152), clip = ppo_epsilon, rho = exp(l - old_log_prob):
+ *                                   loss = -min(adv * rho, adv * clamp(rho, 1 - clip, 1 + clip))
+ *                                   g = -adv * rho where the unclipped term is the smaller or rho is inside the clip, else 0
+ * every mode: loss -= entropy_weight * H.  Outputs: dscores[i, j] = g * (1[j = a] - p_j) / temperature + entropy_weight *
+ * p_j * (logp_j + H) / temperature (pitch ld_dscores); with values: dvalues[i] = 2 * value_scale * (v - returns) and the
+ * value loss value_scale * (v - returns)^2 (value_scale = 1 / N: MSELoss "mean", 1: "sum"); log_prob = l, ratio = e or rho
+ * (1 on policy), advantage [N] (each nullable); policy_partials, value_partials [rg_pg_head_partials(N, A)] whose ordered
+ * sums are the two summed losses (rg_reduce_sum finishes them; no atomics: two runs give the same bits).
+ * A group of 1 / 4 / 16 / 64 lanes per row for A <= 4 / 16 / 64 / 256, four consecutive actions per lane, 16-byte
+ * accesses where pitch and base allow.  The row's arithmetic runs in double on the fp32 inputs (temperature, clip,
+ * entropy_weight and value_scale as the doubles they are passed as) and is rounded once where it is stored.  RG_EINVAL for A < 1, A > RG_PG_MAX_ACTIONS, N < 1, a missing old_log_prob. */
+#define RG_PG_MAX_ACTIONS 256
+enum { RG_PG_REINFORCE = 0, RG_PG_REINFORCE_OFF_POLICY = 1, RG_PG_PPO = 2 };
+int rg_pg_returns(const float* reward, const int32_t* offsets, int num_trajectories, int64_t n, double gamma,
+                  double reward_clip, int normalize, int subtract_mean, int clamp_min, float* out, rg_stream_t stream);
+int rg_pg_head_partials(int n, int num_actions);
+int rg_pg_head(const float* scores, int64_t ld_scores, const float* possible_actions_mask, const void* action,
+               int action_is_int64, int64_t ld_action, const float* returns, const float* values, const float* old_log_prob,
+               double temperature, int mode, double clip, double entropy_weight, double value_scale, int n, int num_actions,
+               float* dscores, int64_t ld_dscores, float* dvalues, float* log_prob, float* ratio, float* advantage,
+               float* policy_partials, float* value_partials, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -287,6 +287,51 @@ class PolicyNetworkInput(BaseInput):
         )
 
 
+@dataclass
+class PolicyGradientInput(TensorDataClass):
+    """One trajectory: state [T, S], action [T, A] one-hot, reward [T], log_prob [T] of the logged action under the
+    acting policy, possible_actions_mask [T, A] (optional).  next_state / not_terminal bootstrap truncated
+    trajectories (the TD-error advantage of the reference's PPO); leave None for complete episodes."""
+
+    state: FeatureData
+    action: torch.Tensor
+    reward: torch.Tensor
+    log_prob: torch.Tensor
+    possible_actions_mask: Optional[torch.Tensor] = None
+    next_state: Optional[FeatureData] = None
+    not_terminal: Optional[torch.Tensor] = None
+
+    @classmethod
+    def input_prototype(cls, action_dim=2, batch_size=10, state_dim=3):
+        return cls(
+            state=FeatureData(float_features=torch.randn(batch_size, state_dim)),
+            action=F.one_hot(torch.randint(high=action_dim, size=(batch_size,)), num_classes=action_dim),
+            reward=torch.rand(batch_size),
+            log_prob=torch.log(torch.rand(batch_size)),
+            possible_actions_mask=torch.ones(batch_size, action_dim),
+        )
+
+    @classmethod
+    def from_dict(cls, d):
+        next_observation = d.get("next_observation", None)
+        return cls(
+            state=FeatureData(float_features=d["observation"]),
+            action=d["action"],
+            reward=d["reward"],
+            log_prob=d["log_prob"],
+            possible_actions_mask=d.get("possible_actions_mask", None),
+            next_state=FeatureData(float_features=next_observation) if next_observation is not None else None,
+            not_terminal=d.get("not_terminal", None),
+        )
+
+    def __len__(self):
+        assert self.action.ndim == 2
+        return len(self.action)
+
+    def batch_size(self):
+        return len(self)
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -308,7 +353,7 @@ USING_REFERENCE_TYPES = False
 _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
-                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput"):
+                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

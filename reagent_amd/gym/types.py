@@ -80,6 +80,21 @@ class Trajectory:
         return out
 
 
+class Sampler:
+    """Given scores, select the action (types.py:110-123)."""
+
+    def sample_action(self, scores: Any):
+        raise NotImplementedError()
+
+    def log_prob(self, scores: Any, action: torch.Tensor) -> torch.Tensor:
+        raise NotImplementedError()
+
+    def update(self) -> None:
+        """Call to update internal parameters (e.g. decay the temperature)"""
+
+
+# From preprocessed observation (and an optional possible-actions mask), produce scores for the sampler (types.py:126-129)
+Scorer = Callable[..., Any]
 # Transform ReplayBuffer's transition batch to the trainer's input type
 TrainerPreprocessor = Callable[[Any], Any]
 # Called after env.step(action)

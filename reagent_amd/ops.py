@@ -620,6 +620,49 @@ def slateq_head(q, qn, wn, reward, reward_mask, not_terminal, gamma, time_diff, 
                                         L.ptr(target), L.ptr(dq), L.ptr(loss_partials), L.ptr(next_q), L.stream_ptr()))
 
 
+def pg_returns(reward, offsets, gamma, reward_clip, normalize: bool, subtract_mean: bool, clamp_min: bool, out):
+    """out [N] = per packed trajectory [offsets[t], offsets[t + 1]) the discounted reward-to-go of clamp(reward, max =
+    reward_clip), whitened (normalize) or mean-subtracted (subtract_mean alone), clamped at 0 from below (clamp_min).
+    offsets: int32 [T + 1] on the device, ascending, offsets[T] = N"""
+    _chk_dev(reward, offsets, out)
+    N, T = reward.numel(), offsets.numel() - 1
+    assert reward.dtype == out.dtype == F32 and reward.is_contiguous() and out.is_contiguous() and out.numel() >= N
+    assert offsets.dtype == torch.int32 and offsets.is_contiguous()
+    _run("rg_pg_returns", dict(N=N, T=T),
+         lambda: L.lib().rg_pg_returns(L.ptr(reward), L.ptr(offsets), T, N, float(gamma), float(reward_clip),
+                                       int(bool(normalize)), int(bool(subtract_mean)), int(bool(clamp_min)), L.ptr(out),
+                                       L.stream_ptr()))
+
+
+def pg_head_partials(n: int, num_actions: int) -> int:
+    return int(L.lib().rg_pg_head_partials(n, num_actions))
+
+
+def pg_head(scores, action, returns, values, old_log_prob, temperature, mode: int, clip, entropy_weight, value_scale, dscores,
+            dvalues, log_prob, ratio, advantage, policy_partials, value_partials, possible_actions_mask=None):
+    """the categorical policy head over [N, A] scores (see rg_pg_head): mode is L.PG_REINFORCE / PG_REINFORCE_OFF_POLICY
+    (clip = clip_param) / PG_PPO (clip = ppo_epsilon); action a one-hot in fp32 or int64; possible_actions_mask [N, A] fp32
+    where the scores do not carry the -1e10 penalty yet.  The ordered sums of the partials are the two summed losses"""
+    _chk_dev(scores, action, returns, values, old_log_prob, dscores, dvalues, log_prob, ratio, advantage, policy_partials,
+             value_partials, possible_actions_mask)
+    N, A = scores.shape
+    assert scores.dtype == dscores.dtype == F32 and dscores.shape == (N, A) and action.shape == (N, A)
+    assert action.dtype in (F32, torch.int64) and action.stride(1) == 1
+    for t in (returns, values, old_log_prob, dvalues, log_prob, ratio, advantage):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.numel() == N)
+    P = pg_head_partials(N, A)
+    assert policy_partials.dtype == F32 and policy_partials.numel() >= P
+    assert value_partials is None or (value_partials.dtype == F32 and value_partials.numel() >= P)
+    m = possible_actions_mask
+    assert m is None or (m.dtype == F32 and m.is_contiguous() and m.shape == (N, A))
+    _run("rg_pg_head", dict(N=N, A=A, mode=mode),
+         lambda: L.lib().rg_pg_head(L.ptr(scores), _ld(scores), L.ptr(m), L.ptr(action), int(action.dtype == torch.int64),
+                                    _ld(action), L.ptr(returns), L.ptr(values), L.ptr(old_log_prob), float(temperature),
+                                    int(mode), float(clip), float(entropy_weight), float(value_scale), N, A, L.ptr(dscores),
+                                    _ld(dscores), L.ptr(dvalues), L.ptr(log_prob), L.ptr(ratio), L.ptr(advantage),
+                                    L.ptr(policy_partials), L.ptr(value_partials), L.stream_ptr()))
+
+
 def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, reward, extra_metrics,
              not_terminal, gamma, gamma_exponent, temperature, num_metrics, loss_type, d_reward_est, d_q_cpe,
              reward_partials, cpe_partials, propensities_out=None):

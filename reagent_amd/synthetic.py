@@ -152,6 +152,36 @@ def to_slateq_input(d: Dict[str, torch.Tensor], device=None):
     return rlt.SlateQInput.from_dict({k: (v.to(device) if device is not None else v) for k, v in d.items()})
 
 
+def pg_trajectory(length: int, state_dim: int, num_actions: int, seed: int = 0, with_mask: bool = False,
+                  behaviour_scale: float = 1.0) -> Dict[str, torch.Tensor]:
+    """One trajectory under the keys rlt.PolicyGradientInput.from_dict reads: observation [T, S], action [T, A] one-hot
+    (int64) drawn from a random behaviour policy (softmax of behaviour_scale * N(0, 1) logits over the allowed actions),
+    log_prob [T] of it under that policy, reward [T] ~ N(0, 1), and with_mask a possible_actions_mask [T, A] (fp32) that
+    always allows the logged action and at least one more"""
+    g = torch.Generator().manual_seed(seed)
+    T, A = length, num_actions
+    obs = torch.randn(T, state_dim, generator=g)
+    logits = torch.randn(T, A, generator=g) * behaviour_scale
+    allowed = torch.ones(T, A, dtype=torch.bool)
+    if with_mask:
+        allowed = torch.rand(T, A, generator=g) < 0.7
+        first = torch.randint(A, (T,), generator=g)
+        allowed[torch.arange(T), first] = True
+        allowed[torch.arange(T), (first + 1 + torch.randint(A - 1, (T,), generator=g)) % A] = True
+    logp = torch.log_softmax(logits.masked_fill(~allowed, float("-inf")), dim=1)
+    a = torch.multinomial(logp.exp(), 1, generator=g).reshape(T)
+    d = dict(observation=obs, action=F.one_hot(a, A), reward=torch.randn(T, generator=g), log_prob=logp[torch.arange(T), a])
+    if with_mask:
+        d["possible_actions_mask"] = allowed.float()
+    return d
+
+
+def to_pg_input(d: Dict[str, torch.Tensor], device=None):
+    from .core import types as rlt
+
+    return rlt.PolicyGradientInput.from_dict({k: (v.to(device) if device is not None else v) for k, v in d.items()})
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 

@@ -7,12 +7,16 @@ from .c51_trainer import C51Trainer  # noqa: F401
 from .discrete_crr_trainer import DiscreteCRRTrainer  # noqa: F401
 from .parametric_dqn_trainer import ParametricDQNTrainer  # noqa: F401
 from .slate_q_trainer import NextSlateValueNormMethod, SlateQTrainer  # noqa: F401
+from .reinforce_trainer import ReinforceTrainer  # noqa: F401
+from .ppo_trainer import PPOTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
     CRRTrainerParameters,
     DQNTrainerParameters,
     ParametricDQNTrainerParameters,
+    PPOTrainerParameters,
     QRDQNTrainerParameters,
+    ReinforceTrainerParameters,
     SACTrainerParameters,
     SlateQTrainerParameters,
     TD3TrainerParameters,

@@ -19,7 +19,9 @@ from .c51_trainer import C51Trainer
 from .discrete_crr_trainer import DiscreteCRRTrainer
 from .dqn_trainer import DQNTrainer
 from .parametric_dqn_trainer import ParametricDQNTrainer
+from .ppo_trainer import PPOTrainer
 from .qrdqn_trainer import QRDQNTrainer
+from .reinforce_trainer import ReinforceTrainer
 from .sac_trainer import SACTrainer
 from .slate_q_trainer import SlateQTrainer
 from .td3_trainer import TD3Trainer
@@ -116,3 +118,13 @@ class QRDQNTrainerParameters:
     "use_gpu", "q_network", "q_network_target", "metrics_to_score", "loss_reporter", "evaluation"])
 class C51TrainerParameters:
     """parameters.py:116-128"""
+
+
+@make_config_class(ReinforceTrainer.__init__, blocklist=["policy", "value_net"])
+class ReinforceTrainerParameters:
+    """parameters.py:131-139"""
+
+
+@make_config_class(PPOTrainer.__init__, blocklist=["policy", "value_net"])
+class PPOTrainerParameters:
+    """parameters.py:142-150"""

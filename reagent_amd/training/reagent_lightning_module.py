@@ -81,6 +81,17 @@ class ReAgentLightningModule(nn.Module):
         one = torch.ones(1, requires_grad=True)
         return one + one
 
+    def optimizers(self, use_pl_optimizer: bool = True):
+        """LightningModule.optimizers() for the manual-optimization trainers (PPO): the optimizers of
+        `configure_optimizers`, made once and in its order (a list, also when there is one)"""
+        if getattr(self, "_manual_optimizers", None) is None:
+            self._manual_optimizers = [o["optimizer"] if isinstance(o, dict) else o for o in self.configure_optimizers()]
+        return self._manual_optimizers
+
+    def manual_backward(self, loss: torch.Tensor, *args, **kwargs):
+        """LightningModule.manual_backward without precision plugins: the loss's backward"""
+        loss.backward(*args, **kwargs)
+
     def log(self, *args, **kwargs):  # LightningModule.log — metrics sink, no-op without Lightning
         pass
 
