@@ -695,6 +695,38 @@ int rg_pg_head(const float* scores, int64_t ld_scores, const float* possible_act
                float* dscores, int64_t ld_dscores, float* dvalues, float* log_prob, float* ratio, float* advantage,
                float* policy_partials, float* value_partials, rg_stream_t stream);
 
+/* ABI 16 — LinUCB contextual bandit (reagent/training/cb/linucb_trainer.py, reagent/models/linear_regression.py).
+ * rg_linucb_accumulate: LinUCBTrainer.update_params (linucb_trainer.py:50-75) on device-resident state, one main launch
+ * and one finishing launch, no host synchronisation.  x [batch, dim] fp32 contiguous (action NULL), or x [batch, arms, dim]
+ * with action [batch] int64: the chosen arm's row is read in place (add_chosen_arm_features, reagent/training/cb/utils.py:
+ * 41-53, without the gathered copy), each index clamped into [0, arms).  y [batch]; weight [batch] or NULL (every weight 1).
+ * State, updated in place: cur_avg_A [dim, dim], cur_avg_b [dim], cur_sum_weight [1] fp32, cur_num_obs [1] int64.
+ * The main launch forms per-workgroup partials of S_A = sum_b w x x^T (v_mfma_f32_32x32x2_f32 on (w * x, x); only the
+ * 32 x 32 tiles on or above the diagonal), S_b = sum_b (w * y) x and s_w = sum_b w over slices of the batch.  The finishing
+ * launch adds the partials in slice order, mirrors the triangle and applies :64-75 in the reference's fp32 operation order
+ * (no contraction): cur_num_obs += batch; cur_sum_weight += s_w; cur_avg = cur_avg * (1 - s_w / cur_sum_weight) + S /
+ * cur_sum_weight.  cur_avg_A leaves exactly symmetric (the entries above the diagonal are the ones read).  No atomics: two
+ * runs give the same bits.  workspace: rg_linucb_workspace_bytes(batch, dim) bytes (0 for arguments the call refuses).
+ * RG_EINVAL for dim < 1, dim > RG_LINUCB_MAX_DIM, batch < 1, a null pointer, arms < 1 with an action, a short workspace.
+ * rg_linucb_score: LinearRegressionUCB._forward_no_coefs_check (linear_regression.py:213-234) over x [n, dim] (n = B *
+ * arms rows): pred_label = x . coefs; pred_sigma = sqrt(x^T inv_avg_A x / sum_weight[0]) (batch_quadratic_form, :41-51;
+ * sum_weight read from DEVICE memory), exactly 0 and not computed for ucb_alpha == 0; ucb = pred_label + ucb_alpha *
+ * pred_sigma.  x * inv_avg_A stays in MFMA accumulators: nothing of size [n, dim] is written.  nan_partials
+ * [rg_linucb_score_partials(n)] int32: rows with a NaN sigma per workgroup.  A finishing launch adds them in order into
+ * nan_count [1] (plain stores, no atomics) and, for arms > 0, writes best_arm [n / arms] int64 = the arg-max of ucb over
+ * each row's arms under arm_presence ([n] bytes, nonzero = present; NULL = all), the lowest index among equals
+ * (get_model_actions, reagent/training/cb/utils.py:113-139, randomize_ties = False); arm 0 for a row with no arm present.
+ * RG_EINVAL for n < 1, dim < 1, dim > RG_LINUCB_MAX_DIM, arms < 0, n not a multiple of arms, a null pointer. */
+#define RG_LINUCB_MAX_DIM 512
+size_t rg_linucb_workspace_bytes(int batch, int dim);
+int rg_linucb_accumulate(const float* x, const int64_t* action, int arms, const float* y, const float* weight, int batch,
+                         int dim, float* cur_avg_A, float* cur_avg_b, float* cur_sum_weight, int64_t* cur_num_obs,
+                         void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_linucb_score_partials(int n);
+int rg_linucb_score(const float* x, const float* coefs, const float* inv_avg_A, const float* sum_weight, double ucb_alpha,
+                    int n, int dim, int arms, const uint8_t* arm_presence, float* pred_label, float* pred_sigma, float* ucb,
+                    int32_t* nan_partials, int32_t* nan_count, int64_t* best_arm, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -332,6 +332,59 @@ class PolicyGradientInput(TensorDataClass):
         return len(self)
 
 
+@dataclass
+class CBInput(TensorDataClass):
+    """A contextual-bandit batch: context_arm_features [B, A, d] (the features of every arm), action [B, 1] int64 (the
+    chosen arm), reward / label [B, 1] (label is what the model is trained on; it defaults to a copy of reward), weight and
+    importance_weight [B, 1] (their product is the row's effective weight), arm_presence [B, A]."""
+
+    context_arm_features: torch.Tensor
+    features_of_chosen_arm: Optional[torch.Tensor] = None
+    chosen_arm_id: Optional[torch.Tensor] = None
+    arm_presence: Optional[torch.Tensor] = None
+    action: Optional[torch.Tensor] = None
+    reward: Optional[torch.Tensor] = None
+    label: Optional[torch.Tensor] = None
+    rewards_all_arms: Optional[torch.Tensor] = None
+    action_log_probability: Optional[torch.Tensor] = None
+    weight: Optional[torch.Tensor] = None
+    importance_weight: Optional[torch.Tensor] = None
+    arms: Optional[torch.Tensor] = None
+    mdp_id: Optional[torch.Tensor] = None
+
+    def __post_init__(self):
+        if self.label is None and self.reward is not None:
+            self.label = self.reward.clone()
+
+    @classmethod
+    def input_prototype(cls, context_dim: int = 2, batch_size: int = 10, arm_features_dim: int = 3, num_arms: int = 4):
+        return cls(context_arm_features=torch.randn(batch_size, num_arms, arm_features_dim))
+
+    @classmethod
+    def from_dict(cls, d):
+        # (rewards_all_arms is not read from the dict: the reference's from_dict leaves it out too)
+        optional = ("features_of_chosen_arm", "chosen_arm_id", "arm_presence", "action", "reward", "label",
+                    "action_log_probability", "weight", "importance_weight", "arms", "mdp_id")
+        return cls(context_arm_features=d["context_arm_features"], **{k: d.get(k, None) for k in optional})
+
+    def __len__(self):
+        return self.context_arm_features.shape[0]
+
+    @property
+    def device(self):
+        return self.context_arm_features.device
+
+    @property
+    def effective_weight(self):
+        weight = self.weight
+        if weight is None:
+            weight = torch.ones(len(self), 1, device=self.device, dtype=torch.float)
+        if self.importance_weight is not None:
+            assert self.importance_weight.shape == weight.shape
+            weight = weight * self.importance_weight
+        return weight
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -353,7 +406,7 @@ USING_REFERENCE_TYPES = False
 _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
-                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput"):
+                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

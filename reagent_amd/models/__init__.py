@@ -10,3 +10,4 @@ from .fully_connected_network import (  # noqa: F401
     set_default_precision,
 )
 from .categorical_dqn import CategoricalDQN  # noqa: F401
+from .linear_regression import LinearRegressionUCB  # noqa: F401

@@ -663,6 +663,66 @@ def pg_head(scores, action, returns, values, old_log_prob, temperature, mode: in
                                     L.ptr(policy_partials), L.ptr(value_partials), L.stream_ptr()))
 
 
+def linucb_workspace(batch: int, dim: int, device) -> torch.Tensor:
+    """the byte workspace rg_linucb_accumulate asks for at (batch, dim)"""
+    n = int(L.lib().rg_linucb_workspace_bytes(int(batch), int(dim)))
+    if n == 0:
+        raise L.ReagentHipError(f"rg_linucb_accumulate does not take batch={batch}, dim={dim} "
+                                f"(1 <= dim <= {L.LINUCB_MAX_DIM}, batch >= 1)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def linucb_accumulate(x, y, weight, cur_avg_A, cur_avg_b, cur_sum_weight, cur_num_obs, workspace, action=None):
+    """LinUCBTrainer.update_params on the device-resident state (see rg_linucb_accumulate), in place.  x [B, d], or
+    x [B, A, d] with action (int64, B entries): the chosen arm's row is read where it lies.  y, weight: B entries each
+    (weight None: ones).  Two launches, no synchronisation."""
+    _chk_dev(x, y, weight, cur_avg_A, cur_avg_b, cur_sum_weight, cur_num_obs, workspace, action)
+    assert x.dtype == F32 and x.is_contiguous() and x.dim() == (3 if action is not None else 2)
+    B, d = x.shape[0], x.shape[-1]
+    arms = x.shape[1] if action is not None else 1
+    assert y.dtype == F32 and y.is_contiguous() and y.numel() == B
+    assert weight is None or (weight.dtype == F32 and weight.is_contiguous() and weight.numel() == B)
+    assert action is None or (action.dtype == torch.int64 and action.is_contiguous() and action.numel() == B)
+    assert cur_avg_A.dtype == F32 and cur_avg_A.is_contiguous() and cur_avg_A.shape == (d, d)
+    assert cur_avg_b.dtype == F32 and cur_avg_b.is_contiguous() and cur_avg_b.numel() == d
+    assert cur_sum_weight.dtype == F32 and cur_sum_weight.numel() == 1
+    assert cur_num_obs.dtype == torch.int64 and cur_num_obs.numel() == 1
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _run("rg_linucb_accumulate", dict(B=B, d=d, arms=arms),
+         lambda: L.lib().rg_linucb_accumulate(L.ptr(x), L.ptr(action), arms, L.ptr(y), L.ptr(weight), B, d, L.ptr(cur_avg_A),
+                                              L.ptr(cur_avg_b), L.ptr(cur_sum_weight), L.ptr(cur_num_obs), L.ptr(workspace),
+                                              workspace.numel(), L.stream_ptr()))
+
+
+def linucb_score_partials(n: int) -> int:
+    return int(L.lib().rg_linucb_score_partials(int(n)))
+
+
+def linucb_score(x, coefs, inv_avg_A, sum_weight, ucb_alpha: float, pred_label, pred_sigma, ucb, nan_partials, nan_count,
+                 arms: int = 0, arm_presence=None, best_arm=None):
+    """LinearRegressionUCB's scores over x [N, d] (see rg_linucb_score): pred_label, pred_sigma, ucb [N]; nan_count [1] int32
+    = rows with a NaN sigma; with arms > 0 (N = B * arms) best_arm [B] int64 = the masked arg-max of ucb over each row's
+    arms (arm_presence: N entries, uint8 or bool)"""
+    m = _u8(arm_presence)
+    _chk_dev(x, coefs, inv_avg_A, sum_weight, pred_label, pred_sigma, ucb, nan_partials, nan_count, m, best_arm)
+    assert x.dtype == F32 and x.is_contiguous() and x.dim() == 2
+    N, d = x.shape
+    assert coefs.dtype == F32 and coefs.is_contiguous() and coefs.numel() == d
+    assert inv_avg_A.dtype == F32 and inv_avg_A.is_contiguous() and inv_avg_A.shape == (d, d)
+    assert sum_weight.dtype == F32 and sum_weight.numel() == 1
+    for t in (pred_label, pred_sigma, ucb):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == N
+    assert nan_partials.dtype == torch.int32 and nan_partials.numel() >= linucb_score_partials(N)
+    assert nan_count.dtype == torch.int32 and nan_count.numel() == 1
+    if arms > 0:
+        assert N % arms == 0 and best_arm.dtype == torch.int64 and best_arm.is_contiguous() and best_arm.numel() == N // arms
+        assert m is None or (m.is_contiguous() and m.numel() == N)
+    _run("rg_linucb_score", dict(N=N, d=d, arms=arms),
+         lambda: L.lib().rg_linucb_score(L.ptr(x), L.ptr(coefs), L.ptr(inv_avg_A), L.ptr(sum_weight), float(ucb_alpha), N, d,
+                                         int(arms), L.ptr(m), L.ptr(pred_label), L.ptr(pred_sigma), L.ptr(ucb),
+                                         L.ptr(nan_partials), L.ptr(nan_count), L.ptr(best_arm), L.stream_ptr()))
+
+
 def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, reward, extra_metrics,
              not_terminal, gamma, gamma_exponent, temperature, num_metrics, loss_type, d_reward_est, d_q_cpe,
              reward_partials, cpe_partials, propensities_out=None):

@@ -1,0 +1,298 @@
+"""rg_linucb_accumulate and rg_linucb_score against the float64 statement of the reference's formulas
+(reagent/training/cb/linucb_trainer.py:64-75, reagent/models/linear_regression.py:213-234), on the interpreter and, under
+`-m gpu`, on the MI355X.  u = 2^-24 throughout.
+
+The bounds are those of fp32 arithmetic in ANY summation order, per entry:
+    |S - S64| <= (B + 2) u sum_b |w x_i x_j|                      (and likewise S_b with |w y x_i|, s_w with |w|)
+    updated average: that bound / cur_sum_weight + 8 u |value|
+    |label - label64| <= (d + 2) u sum_i |x_i c_i|
+    |sigma^2 W - q64| <= (2 d + 8) u sum_ij |x_i M_ij x_j|
+torch's own fp32 `x.t() @ (x * w)` is held to the first one in the same test, so the bound is fair to the reference."""
+import os
+import re
+import subprocess
+
+import pytest
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HIPCC = "/opt/rocm/bin/hipcc"
+U = 2.0 ** -24
+F32, F64 = torch.float32, torch.float64
+
+
+def _batch(B, d, weighted, seed, dev):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, d, generator=g)
+    y = torch.randn(B, generator=g)
+    w = (0.5 + torch.rand(B, generator=g)) if weighted else None
+    return x.to(dev), y.to(dev), None if w is None else w.to(dev)
+
+
+def _fresh(d, dev, sum_weight=1e-5):
+    return [torch.zeros(d, d, device=dev), torch.zeros(d, device=dev), torch.full((1,), sum_weight, device=dev),
+            torch.zeros(1, dtype=torch.int64, device=dev)]
+
+
+def _accumulate(state, x, y, w, action=None):
+    from reagent_amd import ops
+
+    ws = ops.linucb_workspace(x.shape[0], x.shape[-1], x.device)
+    ops.linucb_accumulate(x, y, w, state[0], state[1], state[2], state[3], ws, action=action)
+
+
+def _statement(state, x, y, w):
+    """-> the float64 update of (cur_avg_A, cur_avg_b, cur_sum_weight) from the fp32 state and inputs, the batch sums
+    (S, S_b, s_w) and their absolute sums (the bounds' right-hand sides)"""
+    A0, b0, sw0 = (t.detach().cpu().double() for t in state[:3])
+    x, y = x.detach().cpu().double(), y.detach().cpu().double()
+    w = torch.ones_like(y) if w is None else w.detach().cpu().double()
+    S, Sb, s_w = x.t() @ (x * w[:, None]), x.t() @ (w * y), w.sum()
+    absS, absSb, absw = x.abs().t() @ (x.abs() * w.abs()[:, None]), x.abs().t() @ (w * y).abs(), w.abs().sum()
+    sw1 = sw0 + s_w
+    keep = 1.0 - s_w / sw1
+    return (A0 * keep + S / sw1, b0 * keep + Sb / sw1, sw1), (S, Sb, s_w), (absS, absSb, absw)
+
+
+def _check_update(state_after, want, abs_sums, B, what):
+    (A1, b1, sw1), (absS, absSb, absw) = want, abs_sums
+    got_A, got_b, got_sw = (t.detach().cpu().double() for t in state_after[:3])
+    for name, got, ref, asum in (("cur_avg_A", got_A, A1, absS), ("cur_avg_b", got_b, b1, absSb)):
+        bound = (B + 2) * U * asum / sw1 + 8 * U * ref.abs()
+        over = ((got - ref).abs() - bound).max().item()
+        assert over <= 0, (what, name, over, ((got - ref).abs() / bound.clamp_min(1e-300)).max().item())
+    assert abs(got_sw.item() - sw1.item()) <= (B + 2) * U * absw.item() + 8 * U * abs(sw1.item()), (what, got_sw, sw1)
+
+
+@pytest.mark.parametrize("d", [1, 3, 32, 33, 130])
+@pytest.mark.parametrize("B", [1, 63, 64, 65, 257])
+def test_accumulate_against_float64(backend, B, d):
+    """weights absent and given x an empty state (cur_sum_weight = 1e-5 as constructed, exactly 0 as after an epoch end) and a
+    state an earlier batch left.  Held per entry: the batch sums of torch's own fp32 matmul, the updated averages and the
+    sum of weights; cur_avg_A bitwise symmetric; cur_num_obs exact; a second run bit-identical."""
+    dev = backend.device
+    for weighted in (False, True):
+        x, y, w = _batch(B, d, weighted, 100 * B + d, dev)
+        # the bound is fair to the reference: its fp32 matmul meets it
+        _, (S, Sb, _), (absS, absSb, _) = _statement(_fresh(d, "cpu"), x, y, w)
+        xc, yc = x.cpu(), y.cpu()
+        wc = torch.ones(B) if w is None else w.cpu()
+        ref_S = (xc.t() @ (xc * wc[:, None])).double()
+        ref_Sb = (xc.t() @ (yc * wc)[:, None]).squeeze(1).double()
+        assert ((ref_S - S).abs() <= (B + 2) * U * absS).all() and ((ref_Sb - Sb).abs() <= (B + 2) * U * absSb).all()
+        for kind in ("fresh", "zero", "used"):
+            state = _fresh(d, dev, 0.0 if kind == "zero" else 1e-5)
+            n0 = 0
+            if kind == "used":
+                x0, y0, w0 = _batch(40, d, weighted, 7 + d, dev)
+                _accumulate(state, x0, y0, w0)
+                n0 = 40
+            twin = [t.clone() for t in state]
+            want, sums, abs_sums = _statement(state, x, y, w)
+            _accumulate(state, x, y, w)
+            what = (B, d, weighted, kind)
+            _check_update(state, want, abs_sums, B, what)
+            if kind == "fresh":  # the batch sums themselves: cur_avg * cur_sum_weight from an empty state
+                got_S = state[0].cpu().double() * state[2].cpu().double()
+                assert ((got_S - sums[0]).abs() <= (B + 2) * U * abs_sums[0] + 8 * U * sums[0].abs()).all(), what
+            assert torch.equal(state[0], state[0].t()), what
+            assert state[3].item() == n0 + B, what
+            _accumulate(twin, x, y, w)
+            assert all(torch.equal(a, b) for a, b in zip(state, twin)), what
+
+
+@pytest.mark.gpu
+def test_accumulate_d512_on_the_device():
+    """the largest dimension (16 x 16 tiles, 136 of them computed), B = 300 (two slices): the MI355X only"""
+    import reagent_amd._lib as L
+
+    assert torch.cuda.is_available(), "-m gpu tests need the MI355X"
+    L.lib()
+    B, d = 300, 512
+    x, y, w = _batch(B, d, True, 5, "cuda")
+    state = _fresh(d, "cuda")
+    want, _, abs_sums = _statement(state, x, y, w)
+    _accumulate(state, x, y, w)
+    _check_update(state, want, abs_sums, B, (B, d))
+    assert torch.equal(state[0], state[0].t()) and state[3].item() == B
+
+
+@pytest.mark.parametrize("A", [1, 5])
+def test_accumulate_reads_the_chosen_arm_in_place(backend, A):
+    """[B, A, d] + action is bit-identical to the pre-gathered [B, d] form; an index outside [0, A) is clamped into it"""
+    dev = backend.device
+    B, d = 65, 33
+    g = torch.Generator().manual_seed(A)
+    x3 = torch.randn(B, A, d, generator=g).to(dev)
+    action = torch.randint(0, A, (B,), generator=g).to(dev)
+    y, w = torch.randn(B, generator=g).to(dev), (0.5 + torch.rand(B, generator=g)).to(dev)
+    gathered = torch.gather(x3, 1, action.view(B, 1, 1).expand(-1, 1, d)).squeeze(1).contiguous()
+    a, b = _fresh(d, dev), _fresh(d, dev)
+    _accumulate(a, gathered, y, w)
+    _accumulate(b, x3, y, w, action=action)
+    assert all(torch.equal(s, t) for s, t in zip(a, b))
+    wild = action.clone()
+    wild[0], wild[1] = -3, A + 7
+    clamped = wild.clamp(0, A - 1)
+    c, e = _fresh(d, dev), _fresh(d, dev)
+    _accumulate(c, x3, y, w, action=wild)
+    _accumulate(e, x3, y, w, action=clamped)
+    assert all(torch.equal(s, t) for s, t in zip(c, e))
+
+
+def test_bad_arguments_are_refused(backend):
+    import reagent_amd._lib as L
+
+    lib, dev = L.lib(), backend.device
+    d, B = 4, 8
+    x, y, _ = _batch(B, d, False, 0, dev)
+    st = _fresh(d, dev)
+    ws = torch.empty(1 << 16, dtype=torch.uint8, device=dev)
+    act = torch.zeros(B, dtype=torch.int64, device=dev)
+    p = L.ptr
+
+    def acc(x_=p(x), action=None, arms=1, y_=p(y), B_=B, d_=d, A_=p(st[0]), ws_=p(ws), nbytes=ws.numel()):
+        return lib.rg_linucb_accumulate(x_, action, arms, y_, None, B_, d_, A_, p(st[1]), p(st[2]), p(st[3]), ws_, nbytes, None)
+
+    EINVAL = -1
+    assert acc(d_=0) == EINVAL and acc(d_=513) == EINVAL and acc(B_=0) == EINVAL
+    assert acc(x_=None) == EINVAL and acc(y_=None) == EINVAL and acc(A_=None) == EINVAL and acc(ws_=None) == EINVAL
+    assert acc(action=p(act), arms=0) == EINVAL and acc(nbytes=16) == EINVAL
+    assert lib.rg_linucb_workspace_bytes(B, 0) == 0 and lib.rg_linucb_workspace_bytes(B, 513) == 0
+    assert lib.rg_linucb_workspace_bytes(0, d) == 0 and lib.rg_linucb_workspace_bytes(B, 512) > 0
+    assert torch.equal(st[0], torch.zeros_like(st[0])) and st[3].item() == 0  # nothing ran
+    out = torch.empty(3, B, device=dev)
+    nan = torch.zeros(2, dtype=torch.int32, device=dev)
+    c, M, sw = torch.zeros(d, device=dev), torch.eye(d, device=dev), torch.ones(1, device=dev)
+    best = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    def score(n=B, d_=d, arms=0, x_=p(x), best_=None, nan_=p(nan[:1])):
+        return lib.rg_linucb_score(x_, p(c), p(M), p(sw), 1.0, n, d_, arms, None, p(out[0]), p(out[1]), p(out[2]),
+                                   p(nan[1:]), nan_, best_, None)
+
+    assert score(n=0) == EINVAL and score(d_=0) == EINVAL and score(d_=513) == EINVAL and score(arms=-1) == EINVAL
+    assert score(x_=None) == EINVAL and score(nan_=None) == EINVAL
+    assert score(arms=2, best_=None) == EINVAL and score(arms=3, best_=p(best)) == EINVAL  # 8 rows are no multiple of 3
+    assert score(arms=2, best_=p(best)) == 0
+
+
+def _score(x, coefs, M, sw, alpha, arms=0, presence=None):
+    from reagent_amd import ops
+
+    N, dev = x.shape[0], x.device
+    out = torch.empty(3, N, device=dev)
+    nan = torch.full((ops.linucb_score_partials(N) + 1,), -7, dtype=torch.int32, device=dev)
+    best = torch.full((N // arms,), -7, dtype=torch.int64, device=dev) if arms else None
+    ops.linucb_score(x, coefs, M, sw, alpha, out[0], out[1], out[2], nan[1:], nan[:1], arms=arms, arm_presence=presence,
+                     best_arm=best)
+    return out, int(nan[0].item()), best
+
+
+def _score_inputs(N, d, dev, seed=0):
+    g = torch.Generator().manual_seed(1000 * N + d + seed)
+    x, c = torch.randn(N, d, generator=g), torch.randn(d, generator=g)
+    G = torch.randn(d, d, generator=g)
+    M = G @ G.t() / d + torch.eye(d)
+    M = ((M + M.t()) / 2).contiguous()  # symmetric positive definite
+    return x.to(dev), c.to(dev), M.to(dev), torch.full((1,), 37.5, device=dev)
+
+
+@pytest.mark.parametrize("alpha", [0.0, 1.5])
+@pytest.mark.parametrize("d", [1, 33, 130])
+@pytest.mark.parametrize("N", [1, 65, 5 * 37])
+def test_score_against_float64(backend, N, d, alpha):
+    x, c, M, sw = _score_inputs(N, d, backend.device)
+    out, nan_count, _ = _score(x, c, M, sw, alpha)
+    x64, c64, M64 = x.cpu().double(), c.cpu().double(), M.cpu().double()
+    label, sigma, ucb = (t.cpu() for t in out)
+    assert ((label.double() - x64 @ c64).abs() <= (d + 2) * U * (x64.abs() @ c64.abs())).all()
+    assert nan_count == 0
+    if alpha == 0.0:
+        assert torch.equal(sigma, torch.zeros(N)) and torch.equal(ucb, label)  # exactly 0, not a small number
+    else:
+        q64 = ((x64 @ M64) * x64).sum(-1)
+        qabs = ((x64.abs() @ M64.abs()) * x64.abs()).sum(-1)
+        assert ((sigma.double() ** 2 * sw.cpu().double() - q64).abs() <= (2 * d + 8) * U * qabs).all()
+        assert torch.equal(ucb, label + torch.tensor(alpha) * sigma)  # one multiply and one add in fp32
+    again, _, _ = _score(x, c, M, sw, alpha)
+    assert torch.equal(out, again)
+
+
+@pytest.mark.parametrize("B,arms", [(1, 1), (13, 5), (37, 5)])
+@pytest.mark.parametrize("masked", [False, True])
+def test_best_arm_is_the_masked_argmax_of_the_kernels_ucb(backend, B, arms, masked):
+    """N = 1, 65 and 5 * 37 rows as B rows of `arms` arms: best_arm equals torch.argmax of the kernel's own ucb under the
+    mask.  Rows 0 and 2 carry a planted exact tie at their maximum (two arms with the same large features: the lower index
+    wins); with a mask, row 1 has no arm present and gets arm 0."""
+    dev, d = backend.device, 33
+    x, c, M, sw = _score_inputs(B * arms, d, dev, seed=3)
+    x = x.view(B, arms, d)
+    if arms > 2:
+        for b in (0, 2):
+            x[b, 3] = x[b, 1] = 4.0 * c / c.norm()
+    presence = None
+    if masked:
+        g = torch.Generator().manual_seed(B)
+        presence = (torch.rand(B, arms, generator=g) < 0.6).to(dev)
+        if arms > 2:
+            presence[0, 1] = presence[0, 3] = True
+            presence[2, 1] = False  # the tie's lower arm is absent: the higher one is the answer
+            presence[2, 3] = True
+            presence[1] = False
+    out, _, best = _score(x.reshape(B * arms, d).contiguous(), c, M, sw, 1.5, arms=arms,
+                          presence=None if presence is None else presence.reshape(-1))
+    ucb = out[2].view(B, arms)
+    if arms > 2:
+        assert ucb[0, 1] == ucb[0, 3] and ucb[0, 1] == ucb[0].max()
+    want = (ucb if presence is None else torch.where(presence, ucb, torch.full_like(ucb, float("-inf")))).argmax(1)
+    assert torch.equal(best, want)
+    if arms > 2:
+        assert best[0].item() == 1 and best[2].item() == (3 if masked else 1)
+        if masked:
+            assert best[1].item() == 0
+    from reagent_amd.training.cb import get_model_actions
+
+    assert torch.equal(get_model_actions(ucb, presence), want.view(-1, 1))
+
+
+def test_negative_definite_matrix_counts_every_row_and_forward_raises(backend):
+    dev, N, d = backend.device, 65, 33
+    x, c, _, sw = _score_inputs(N, d, dev)
+    out, nan_count, _ = _score(x, c, -torch.eye(d, device=dev), sw, 1.5)
+    assert nan_count == N and torch.isnan(out[1]).all()
+    from reagent_amd.models.linear_regression import LinearRegressionUCB
+
+    m = LinearRegressionUCB(d).to(dev)
+    m.inv_avg_A.copy_(-torch.eye(d))
+    m.sum_weight.fill_(1.0)
+    m._coefs_dirty = False
+    with pytest.raises(Exception, match="pred_sigma has nan values"):
+        m(x)
+    with pytest.raises(Exception, match="pred_sigma has nan values"):
+        m.forward_inference(x)
+    assert set(m(x, ucb_alpha=0.0)) == {"pred_label", "pred_sigma", "ucb"}  # the mean alone never reads the matrix
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
+def test_cb_kernels_have_no_scratch(tmp_path):
+    """cb.hip compiled for gfx950 with the resource remarks on: its four kernels, no scratch, no spilled register"""
+    csrc = os.path.join(ROOT, "reagent_amd", "csrc")
+    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{csrc}", f"-I{ROOT}/include",
+                          "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "cb.hip"),
+                          "-o", str(tmp_path / "o.o")], capture_output=True, text=True, timeout=900)
+    assert out.returncode == 0, out.stderr[-2000:]
+    kernels, name = {}, None
+    for line in out.stderr.splitlines():
+        m = re.search(r"Function Name: (\S+)", line)
+        if m:
+            name = m.group(1)
+            kernels[name] = {}
+        for key in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]"):
+            m = re.search(re.escape(key) + r": (\d+)", line)
+            if m and name:
+                kernels[name].setdefault(key, int(m.group(1)))
+    for want in ("linucb_gram_kernel", "linucb_finish_kernel", "linucb_score_kernel", "linucb_select_kernel"):
+        assert sum(want in k for k in kernels) == 1, (want, list(kernels))
+    assert len(kernels) == 4
+    for k, v in kernels.items():
+        assert v.get("VGPRs Spill", 0) == 0 and v.get("SGPRs Spill", 0) == 0 and v["ScratchSize [bytes/lane]"] == 0, (k, v)
