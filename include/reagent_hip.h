@@ -727,6 +727,44 @@ int rg_linucb_score(const float* x, const float* coefs, const float* inv_avg_A, 
                     int n, int dim, int arms, const uint8_t* arm_presence, float* pred_label, float* pred_sigma, float* ucb,
                     int32_t* nan_partials, int32_t* nan_count, int64_t* best_arm, rg_stream_t stream);
 
+/* ABI 17 — disjoint LinUCB: one ridge regression per arm (reagent/training/cb/disjoint_linucb_trainer.py,
+ * reagent/models/disjoint_linucb_predictor.py).
+ * rg_dlinucb_accumulate: DisjointLinUCBTrainer.cb_training_step (disjoint_linucb_trainer.py:88-101: a Python loop of
+ * update_params, :46-76, over the arms) for ALL arms in one main and one finishing launch, no host synchronisation.
+ * x [n, dim] fp32 contiguous, y [n], weight [n] or NULL (every weight 1): the arms' sub-batches back to back in arm order;
+ * row_offsets [arms + 1] int64 in DEVICE memory: arm a's rows are [row_offsets[a], row_offsets[a + 1]) (forced into
+ * 0 <= begin <= end <= n where they are not; an empty range is legal).  max_arm_rows is a HOST hint, the longest sub-batch:
+ * it sizes the grid and the workspace and never decides which rows count (the last slice of an arm runs to the arm's end).
+ * State, updated in place: cur_A [arms, dim, dim], cur_b [arms, dim] fp32, cur_num_obs [arms] int64.  The main launch forms,
+ * per (tile on or above the diagonal, slice of the arm's rows, arm), partials of S_A = sum w x x^T (v_mfma_f32_32x32x2_f32 on
+ * (w * x, x)) and S_b = sum (w * y) x; a workgroup whose slice is empty writes zeros.  The finishing launch adds an arm's
+ * slices in order, mirrors the triangle, and does cur_A[a] += S_A, cur_b[a] += S_b (one fp32 add each; cur_A[a] leaves
+ * exactly symmetric: the entries above the diagonal are the ones read) and cur_num_obs[a] += n_a.  No atomics: two runs give
+ * the same bits.  Where an arm's rows are cut into slices depends on dim alone, so an arm's result depends only on its own
+ * rows — not on where they lie in the packed batch, on the other arms or (while the hint is not too short and the launch has
+ * under 2^20 workgroups) on max_arm_rows: a call with arms = 1 on one arm's rows and that arm's slice of the state gives the
+ * bits of the packed call.  workspace: rg_dlinucb_workspace_bytes(max_arm_rows, arms, dim) bytes (0 for arguments the call
+ * refuses).  n == 0 is legal and changes nothing.  RG_EINVAL for dim < 1, dim > RG_LINUCB_MAX_DIM, arms < 1, arms > 65535,
+ * n < 0, max_arm_rows < 0, a null pointer (weight excepted; x and y too where n == 0), a short workspace.
+ * rg_dlinucb_score: DisjointLinearRegressionUCB.forward (disjoint_linucb_predictor.py:149-174, with
+ * batch_quadratic_form_multi_arms, :17-31) over x [batch, dim]: mean[r, a] = x_r . coefs[a] (coefs [arms, dim]);
+ * sigma[r, a] = sqrt(x_r^T inv_A[a] x_r) (inv_A [arms, dim, dim]; no division by a weight, no NaN check: a negative form is
+ * NaN, silently); ucb = mean + float(ucb_alpha) * sigma, one multiply and one add.  ucb_alpha == 0: inv_A is not read, sigma
+ * is exactly 0 and ucb has the bits of mean.  ucb [batch, arms] is required; mean and sigma [batch, arms] may be NULL.
+ * best_arm [batch] int64 (or NULL), from the same launch: the arg-max of ucb over the arms arm_presence ([batch, arms] bytes,
+ * nonzero = present; NULL = all) marks present, the lowest index among equals, a NaN before any number (rg_linucb_score's
+ * rule), arm 0 for a row with no arm present (get_model_actions, reagent/training/cb/utils.py:113-139).  A workgroup stages
+ * its rows of x in LDS once and reuses them for every arm; x * inv_A[a] stays in MFMA accumulators.  One launch.
+ * RG_EINVAL for batch < 1, arms < 1, dim < 1, dim > RG_LINUCB_MAX_DIM, batch * arms >= 2^31, a null x / coefs / inv_A / ucb,
+ * arm_presence without best_arm. */
+size_t rg_dlinucb_workspace_bytes(int max_arm_rows, int arms, int dim);
+int rg_dlinucb_accumulate(const float* x, const float* y, const float* weight, const int64_t* row_offsets, int n, int arms,
+                          int max_arm_rows, int dim, float* cur_A, float* cur_b, int64_t* cur_num_obs, void* workspace,
+                          size_t workspace_bytes, rg_stream_t stream);
+int rg_dlinucb_score(const float* x, const float* coefs, const float* inv_A, double ucb_alpha, int batch, int dim, int arms,
+                     const uint8_t* arm_presence, float* mean, float* sigma, float* ucb, int64_t* best_arm,
+                     rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

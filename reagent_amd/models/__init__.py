@@ -11,3 +11,4 @@ from .fully_connected_network import (  # noqa: F401
 )
 from .categorical_dqn import CategoricalDQN  # noqa: F401
 from .linear_regression import LinearRegressionUCB  # noqa: F401
+from .disjoint_linucb_predictor import DisjointLinearRegressionUCB  # noqa: F401

@@ -723,6 +723,57 @@ def linucb_score(x, coefs, inv_avg_A, sum_weight, ucb_alpha: float, pred_label, 
                                          L.ptr(nan_partials), L.ptr(nan_count), L.ptr(best_arm), L.stream_ptr()))
 
 
+def dlinucb_workspace(max_arm_rows: int, arms: int, dim: int, device) -> torch.Tensor:
+    """the byte workspace rg_dlinucb_accumulate asks for at (max_arm_rows, arms, dim)"""
+    n = int(L.lib().rg_dlinucb_workspace_bytes(int(max_arm_rows), int(arms), int(dim)))
+    if n == 0:
+        raise L.ReagentHipError(f"rg_dlinucb_accumulate does not take max_arm_rows={max_arm_rows}, arms={arms}, dim={dim} "
+                                f"(1 <= dim <= {L.LINUCB_MAX_DIM}, 1 <= arms <= 65535, max_arm_rows >= 0)")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def dlinucb_accumulate(x, y, weight, row_offsets, max_arm_rows: int, cur_A, cur_b, cur_num_obs, workspace):
+    """DisjointLinUCBTrainer.cb_training_step on the device-resident state (see rg_dlinucb_accumulate), in place.  x [N, d],
+    y and weight N entries each (weight None: ones): the arms' sub-batches back to back; row_offsets [arms + 1] int64 on the
+    device; max_arm_rows: the longest sub-batch (a hint).  cur_A [arms, d, d], cur_b [arms, d], cur_num_obs [arms] int64.
+    Two launches, no synchronisation."""
+    _chk_dev(x, y, weight, row_offsets, cur_A, cur_b, cur_num_obs, workspace)
+    assert x.dtype == F32 and x.is_contiguous() and x.dim() == 2
+    N, d = x.shape
+    assert row_offsets.dtype == torch.int64 and row_offsets.is_contiguous() and row_offsets.numel() >= 2
+    arms = row_offsets.numel() - 1
+    assert y.dtype == F32 and y.is_contiguous() and y.numel() == N
+    assert weight is None or (weight.dtype == F32 and weight.is_contiguous() and weight.numel() == N)
+    assert cur_A.dtype == F32 and cur_A.is_contiguous() and cur_A.shape == (arms, d, d)
+    assert cur_b.dtype == F32 and cur_b.is_contiguous() and cur_b.shape == (arms, d)
+    assert cur_num_obs.dtype == torch.int64 and cur_num_obs.is_contiguous() and cur_num_obs.numel() == arms
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _run("rg_dlinucb_accumulate", dict(N=N, d=d, arms=arms),
+         lambda: L.lib().rg_dlinucb_accumulate(L.ptr(x), L.ptr(y), L.ptr(weight), L.ptr(row_offsets), N, arms,
+                                               int(max_arm_rows), d, L.ptr(cur_A), L.ptr(cur_b), L.ptr(cur_num_obs),
+                                               L.ptr(workspace), workspace.numel(), L.stream_ptr()))
+
+
+def dlinucb_score(x, coefs, inv_A, ucb_alpha: float, ucb, mean=None, sigma=None, arm_presence=None, best_arm=None):
+    """DisjointLinearRegressionUCB.forward over x [B, d] (see rg_dlinucb_score): ucb (and mean, sigma where given) [B, arms];
+    best_arm [B] int64 = the arg-max of ucb over the arms arm_presence ([B, arms] uint8 or bool; None: all) marks present"""
+    m = _u8(arm_presence)
+    _chk_dev(x, coefs, inv_A, ucb, mean, sigma, m, best_arm)
+    assert x.dtype == F32 and x.is_contiguous() and x.dim() == 2
+    B, d = x.shape
+    assert coefs.dtype == F32 and coefs.is_contiguous() and coefs.dim() == 2 and coefs.shape[1] == d
+    arms = coefs.shape[0]
+    assert inv_A.dtype == F32 and inv_A.is_contiguous() and inv_A.shape == (arms, d, d)
+    for t in (ucb, mean, sigma):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == (B, arms))
+    assert ucb is not None
+    assert best_arm is None or (best_arm.dtype == torch.int64 and best_arm.is_contiguous() and best_arm.numel() == B)
+    assert m is None or (best_arm is not None and m.numel() == B * arms)
+    _run("rg_dlinucb_score", dict(B=B, d=d, arms=arms),
+         lambda: L.lib().rg_dlinucb_score(L.ptr(x), L.ptr(coefs), L.ptr(inv_A), float(ucb_alpha), B, d, arms, L.ptr(m),
+                                          L.ptr(mean), L.ptr(sigma), L.ptr(ucb), L.ptr(best_arm), L.stream_ptr()))
+
+
 def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, reward, extra_metrics,
              not_terminal, gamma, gamma_exponent, temperature, num_metrics, loss_type, d_reward_est, d_q_cpe,
              reward_partials, cpe_partials, propensities_out=None):

@@ -16,6 +16,7 @@ class BaseCBTrainerWithEval(ReAgentLightningModule):
     """A subclass implements cb_training_step(); training_step() is final: it checks the batch and hands it on."""
 
     scorer: torch.nn.Module
+    takes_list_batch = False  # a trainer of the disjoint models (a List[CBInput], one batch per arm) declares True
 
     def __init__(self, eval_model_update_critical_weight: Optional[float] = None, recmetric_module=None,
                  log_every_n_steps: int = 0, *args, **kwargs):
@@ -53,7 +54,8 @@ class BaseCBTrainerWithEval(ReAgentLightningModule):
     def training_step(self, batch: CBInput, batch_idx: int, optimizer_idx: int = 0) -> Optional[torch.Tensor]:
         """base_trainer.py:84-145 with no evaluation module: check the batch, then cb_training_step on it.  The features of
         the chosen arm are NOT gathered here (add_chosen_arm_features): the trainer's kernel reads them in place."""
-        refuse_disjoint(batch)
+        if not self.takes_list_batch:
+            refuse_disjoint(batch)
         if self.eval_module is not None:
             raise NotImplementedError("an attached eval_module (offline evaluation inside the training loop) is not "
                                       "implemented")
