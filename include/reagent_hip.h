@@ -765,6 +765,53 @@ int rg_dlinucb_score(const float* x, const float* coefs, const float* inv_A, dou
                      const uint8_t* arm_presence, float* mean, float* sigma, float* ucb, int64_t* best_arm,
                      rg_stream_t stream);
 
+/* ABI 18 — deep-represent LinUCB: an MLP's output under a LinUCB layer (reagent/models/deep_represent_linucb.py,
+ * reagent/training/cb/deep_represent_linucb_trainer.py).
+ * rg_linucb_solve: LinearRegressionUCB._calculate_coefs (reagent/models/linear_regression.py:157-199, one process) on
+ * device-resident state in ONE launch of one workgroup, no host synchronisation, for 1 <= dim <= RG_LINUCB_SOLVE_MAX_DIM.
+ * The deep model runs it on every training step (deep_represent_linucb.py:148-151: cur_avg_A is non-zero after every
+ * update_params).  Fold (reduce_avg, :54-89) in the reference's fp32 operation order, no contraction, bit for bit:
+ * total = cur_sum_weight + sum_weight; avg_A = (avg_A * sum_weight + cur_avg_A * cur_sum_weight) / total, likewise avg_b;
+ * num_obs += cur_num_obs; sum_weight += cur_sum_weight.  A_ext = avg_A + float(l2_reg_lambda) * I / sum_weight (the diagonal
+ * gets (lambda * 1) / sum_weight in fp32, the rest of avg_A is taken as it is).  inv_avg_A = A_ext^-1 by Gauss-Jordan
+ * elimination without pivoting (A_ext is symmetric positive definite for lambda > 0): the matrix lives in the registers of
+ * a 16 x 16 grid of threads (entry (i, j) with thread (i % 16, j % 16); 1, 4, 16 or 64 entries a thread for dim <= 16 / 32 /
+ * 64 / 128); every step publishes the pivot row and column through LDS (2.5 KB) and costs one barrier.  coefs = inv_avg_A * avg_b; coefs_valid_for_avg_A = avg_A;
+ * cur_avg_A, cur_avg_b, cur_sum_weight and cur_num_obs leave exactly zero.  status [1] int32 is STICKY: set to 1 where a
+ * pivot is not positive or not finite (the call still runs all dim steps and writes finite-or-NaN values; a caller that
+ * finds it set recomputes on the host from the folded avg_A and clears it), never written otherwise.  No atomics: two runs
+ * give the same bits.  RG_EINVAL for dim < 1, dim > RG_LINUCB_SOLVE_MAX_DIM, a null pointer.
+ * rg_drlinucb_head: what DeepRepresentLinearRegressionUCB.forward (deep_represent_linucb.py:136-152, 165) and
+ * DeepRepresentLinUCBTrainer.cb_training_step (deep_represent_linucb_trainer.py:81-89) do after the MLP, and autograd's
+ * backward of it.  mlp_out [batch, h] fp32 (pitch ld_mlp_out); v [h + 1] = linear_layer.weight[0] (nn_e2e) or _coefs.
+ * Always written: z [batch, h + 1] contiguous = [1, mlp_out] (mlp_out_with_ones: what forward returns and
+ * rg_linucb_accumulate / rg_linucb_score read), lin [batch] = z . v, pred_label [batch] = act(lin) (act an RG_ACT_* code,
+ * the FC epilogues' functions).  label == NULL is the forward-only mode: nothing else is written and no finishing launch
+ * follows.  With label [batch] (weight [batch] or NULL: every weight 1), loss_type RG_CB_LOSS_MSE (p - y)^2, RG_CB_LOSS_MAE
+ * |p - y|, RG_CB_LOSS_BCE -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) (F.binary_cross_entropy):
+ * row_loss [batch] = loss_r * w_r; loss [1] = sum_r row_loss / batch; with g_r = 2 (p - y), sign(p - y) (sign(0) = 0),
+ * (p - y) / max(p (1 - p), 1e-12) and dlin_r = g_r * (w_r / batch) * act'(lin_r): dmlp_out [batch, h] (pitch ld_dmlp_out)
+ * = dlin_r * v[1:], and, where dv is not NULL (nn_e2e), dv [h + 1] = sum_r dlin_r * z_r.  The main launch leaves
+ * per-workgroup partials (loss_partials [P], dv_partials [P, h + 1], P = rg_drlinucb_head_partials(batch, h)); a finishing
+ * launch adds them in a fixed order (in double) into loss and dv.  No atomics: two runs give the same bits.  1 / 4 / 16 /
+ * 64 lanes per row for h <= 4 / 16 / 64 / more.  RG_EINVAL for batch < 1, h < 1, h + 1 > RG_LINUCB_MAX_DIM, a pitch below
+ * h, an unknown act or loss_type, a null mlp_out / v / z / lin / pred_label, and with a label a null row_loss / dmlp_out /
+ * loss_partials / loss, or dv without dv_partials.
+ * rg_drlinucb_activate: a[i] = act(a[i]) and (b not NULL) b[i] = act(b[i]) for i < n, one launch: the output activation on
+ * pred_label and ucb after rg_linucb_score (deep_represent_linucb.py:165-166, 202-204).  RG_EINVAL for n < 1, a null a, an
+ * unknown act. */
+#define RG_LINUCB_SOLVE_MAX_DIM 128
+enum { RG_CB_LOSS_MSE = 0, RG_CB_LOSS_MAE = 1, RG_CB_LOSS_BCE = 2 };
+int rg_linucb_solve(int dim, double l2_reg_lambda, float* avg_A, float* avg_b, float* sum_weight, int64_t* num_obs,
+                    float* cur_avg_A, float* cur_avg_b, float* cur_sum_weight, int64_t* cur_num_obs, float* inv_avg_A,
+                    float* coefs, float* coefs_valid_for_avg_A, int32_t* status, rg_stream_t stream);
+int rg_drlinucb_head_partials(int batch, int h);
+int rg_drlinucb_head(const float* mlp_out, int64_t ld_mlp_out, const float* v, const float* label, const float* weight,
+                     int act, int loss_type, int batch, int h, float* z, float* lin, float* pred_label, float* row_loss,
+                     float* dmlp_out, int64_t ld_dmlp_out, float* loss_partials, float* dv_partials, float* loss, float* dv,
+                     rg_stream_t stream);
+int rg_drlinucb_activate(float* a, float* b, int n, int act, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

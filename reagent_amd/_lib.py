@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RG_LIB: another build of the same library (same-box A/B of compile-time kernel variants); default = the in-tree build
 LIB_PATH = os.environ.get("RG_LIB") or os.path.join(_HERE, "lib", "libreagent_hip.so")
 
-ABI_VERSION = 17  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
+ABI_VERSION = 18  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT = {"linear": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}
@@ -25,6 +25,8 @@ SLATE_MAX_CANDIDATES = 1024  # RG_SLATE_MAX_CANDIDATES: rg_slate_topk's limit on
 PG_MAX_ACTIONS = 256  # RG_PG_MAX_ACTIONS: rg_pg_head's limit on A
 PG_REINFORCE, PG_REINFORCE_OFF_POLICY, PG_PPO = 0, 1, 2  # RG_PG_*: rg_pg_head's modes
 LINUCB_MAX_DIM = 512  # RG_LINUCB_MAX_DIM: the LinUCB kernels' limit on the feature dimension
+LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (the matrix lives in one workgroup's registers)
+CB_LOSS = {"mse": 0, "mae": 1, "cross_entropy": 2}  # RG_CB_LOSS_*: rg_drlinucb_head's losses under the reference's LOSS_TYPES names
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
     ctypes.c_void_p,
@@ -257,6 +259,11 @@ SIGNATURES = {
     "rg_dlinucb_workspace_bytes": (c_sz, [c_int, c_int, c_int]),
     "rg_dlinucb_accumulate": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3 + [c_void_p, c_sz, c_void_p]),
     "rg_dlinucb_score": (c_int, [c_void_p] * 3 + [c_d, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
+    "rg_linucb_solve": (c_int, [c_int, c_d] + [c_void_p] * 12 + [c_void_p]),
+    "rg_drlinucb_head_partials": (c_int, [c_int, c_int]),
+    "rg_drlinucb_head": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, c_void_p, c_i64] + [c_void_p] * 4 + [c_void_p]),
+    "rg_drlinucb_activate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rg_bcq_filter": (c_int, [c_void_p, c_int, c_int, c_d, c_void_p, c_void_p]),
     "rg_dqn_head_partials": (c_int, [c_int]),
     "rg_dqn_pair_wave_sums": (c_int, [c_int]),

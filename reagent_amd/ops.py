@@ -723,6 +723,70 @@ def linucb_score(x, coefs, inv_avg_A, sum_weight, ucb_alpha: float, pred_label, 
                                          L.ptr(nan_partials), L.ptr(nan_count), L.ptr(best_arm), L.stream_ptr()))
 
 
+def linucb_solve(l2_reg_lambda: float, avg_A, avg_b, sum_weight, num_obs, cur_avg_A, cur_avg_b, cur_sum_weight, cur_num_obs,
+                 inv_avg_A, coefs, coefs_valid_for_avg_A, status):
+    """LinearRegressionUCB._calculate_coefs on the device-resident buffers (see rg_linucb_solve), in place: one launch, no
+    synchronisation.  status [1] int32 is sticky: 1 after a pivot that was not positive or not finite"""
+    _chk_dev(avg_A, avg_b, sum_weight, num_obs, cur_avg_A, cur_avg_b, cur_sum_weight, cur_num_obs, inv_avg_A, coefs,
+             coefs_valid_for_avg_A, status)
+    d = avg_A.shape[0]
+    for t in (avg_A, cur_avg_A, inv_avg_A, coefs_valid_for_avg_A):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (d, d)
+    for t in (avg_b, cur_avg_b, coefs):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == d
+    for t in (sum_weight, cur_sum_weight):
+        assert t.dtype == F32 and t.numel() == 1
+    for t in (num_obs, cur_num_obs):
+        assert t.dtype == torch.int64 and t.numel() == 1
+    assert status.dtype == torch.int32 and status.numel() == 1
+    _run("rg_linucb_solve", dict(d=d),
+         lambda: L.lib().rg_linucb_solve(d, float(l2_reg_lambda), L.ptr(avg_A), L.ptr(avg_b), L.ptr(sum_weight), L.ptr(num_obs),
+                                         L.ptr(cur_avg_A), L.ptr(cur_avg_b), L.ptr(cur_sum_weight), L.ptr(cur_num_obs),
+                                         L.ptr(inv_avg_A), L.ptr(coefs), L.ptr(coefs_valid_for_avg_A), L.ptr(status),
+                                         L.stream_ptr()))
+
+
+def drlinucb_head_partials(batch: int, h: int) -> int:
+    return int(L.lib().rg_drlinucb_head_partials(int(batch), int(h)))
+
+
+def drlinucb_head(mlp_out, v, act: int, z, lin, pred_label, label=None, weight=None, loss_type: int = 0, row_loss=None,
+                  dmlp_out=None, loss_partials=None, dv_partials=None, loss=None, dv=None):
+    """the deep-represent LinUCB head over mlp_out [B, h] (see rg_drlinucb_head): z [B, h + 1] = [1, mlp_out], lin = z . v,
+    pred_label = act(lin); with a label also row_loss [B], loss [1], dmlp_out [B, h] and (dv given) dv [h + 1].  label None
+    is the forward-only mode"""
+    _chk_dev(mlp_out, v, z, lin, pred_label, label, weight, row_loss, dmlp_out, loss_partials, dv_partials, loss, dv)
+    B, h = mlp_out.shape
+    assert mlp_out.dtype == F32 and v.dtype == F32 and v.is_contiguous() and v.numel() == h + 1
+    assert z.dtype == F32 and z.is_contiguous() and z.shape == (B, h + 1)
+    for t in (lin, pred_label, label, weight, row_loss):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.numel() == B)
+    ldd = 0
+    if label is not None:
+        P = drlinucb_head_partials(B, h)
+        assert dmlp_out.dtype == F32 and dmlp_out.shape == (B, h) and row_loss is not None
+        ldd = _ld(dmlp_out)
+        assert loss_partials.dtype == F32 and loss_partials.is_contiguous() and loss_partials.numel() >= P
+        assert loss.dtype == F32 and loss.numel() == 1
+        if dv is not None:
+            assert dv.dtype == F32 and dv.is_contiguous() and dv.numel() == h + 1
+            assert dv_partials.dtype == F32 and dv_partials.is_contiguous() and dv_partials.numel() >= P * (h + 1)
+    _run("rg_drlinucb_head", dict(B=B, h=h, train=label is not None),
+         lambda: L.lib().rg_drlinucb_head(L.ptr(mlp_out), _ld(mlp_out), L.ptr(v), L.ptr(label), L.ptr(weight), int(act),
+                                          int(loss_type), B, h, L.ptr(z), L.ptr(lin), L.ptr(pred_label), L.ptr(row_loss),
+                                          L.ptr(dmlp_out), ldd, L.ptr(loss_partials), L.ptr(dv_partials), L.ptr(loss),
+                                          L.ptr(dv), L.stream_ptr()))
+
+
+def drlinucb_activate(a, b, act: int):
+    """a = act(a) and (b given) b = act(b) in place, one launch (see rg_drlinucb_activate)"""
+    _chk_dev(a, b)
+    n = a.numel()
+    assert a.dtype == F32 and a.is_contiguous() and (b is None or (b.dtype == F32 and b.is_contiguous() and b.numel() == n))
+    _run("rg_drlinucb_activate", dict(n=n),
+         lambda: L.lib().rg_drlinucb_activate(L.ptr(a), L.ptr(b), n, int(act), L.stream_ptr()))
+
+
 def dlinucb_workspace(max_arm_rows: int, arms: int, dim: int, device) -> torch.Tensor:
     """the byte workspace rg_dlinucb_accumulate asks for at (max_arm_rows, arms, dim)"""
     n = int(L.lib().rg_dlinucb_workspace_bytes(int(max_arm_rows), int(arms), int(dim)))
