@@ -812,6 +812,37 @@ int rg_drlinucb_head(const float* mlp_out, int64_t ld_mlp_out, const float* v, c
                      rg_stream_t stream);
 int rg_drlinucb_activate(float* a, float* b, int n, int act, rg_stream_t stream);
 
+/* ABI 19 — offline policy evaluation inside the contextual-bandit training loop: the replay estimator of Li et al.
+ * (arXiv 1003.0146, Algorithm 3), reagent/evaluation/cb/policy_evaluator.py, base_evaluator.py, utils.py.
+ * rg_cb_eval_ingest: BaseOfflineEval.ingest_batch (base_evaluator.py:147-169) = PolicyEvaluator._process_all_data
+ * (policy_evaluator.py:22-35), add_importance_weights (evaluation/cb/utils.py:9-47) and _process_used_data
+ * (policy_evaluator.py:38-68), plus sum_weight_since_update_local += ... (reagent/training/cb/base_trainer.py:127-129), in
+ * one main and one finishing launch on device-resident state, no atomics, no host synchronisation.  action, model_action
+ * [batch] int64 (model_action is rg_linucb_score's best_arm as it is); reward [batch] fp32; weight [batch] or NULL (every
+ * weight 1); action_log_probability [batch] or NULL; arm_presence [batch, arms] bytes (nonzero = present) or NULL.  Per row,
+ * every operation rounded to fp32 on its own: size = the row's count of present arms (arms without arm_presence);
+ * p = exp(logp), or 1.0f / size without log-probabilities; iw = 1.0f / p (two IEEE divisions); with clip != 0
+ * iw = iw > float(max_importance_weight) ? that : iw (torch.clamp(max=): a NaN passes); importance_weight = (action ==
+ * model_action ? 1.0f : 0.0f) * iw — a multiplication: 0 * inf is NaN, as in the reference; effective_weight = w *
+ * importance_weight (what rg_linucb_accumulate / rg_drlinucb_head take as their weight); acc = importance_weight > 0.
+ * The nine one-element fp32 buffers each receive their sum over the batch, in the order of the arguments: w; w * reward;
+ * w * size; eff * reward; (w * acc) * reward; w * acc; eff; (w * acc) * size; and w again into sum_weight_since_update.
+ * The main launch leaves per-workgroup (256 rows) partials in double in `partials` (8 * rg_cb_eval_ingest_partials(batch)
+ * doubles); the finishing launch adds them in a fixed order and adds each total to its buffer with ONE rounding to fp32:
+ * two runs give the same bits.  KEPT QUIRK of the reference: without arm_presence its `sizes` [B, 1] times
+ * `weights.squeeze()` [B] broadcasts to [B, B], so the two size sums are `batch` times too large (B * arms * sum w); they are
+ * here too.  With arm_presence they are the plain sums.  RG_EINVAL for batch < 1, arms < 1, a null action / model_action /
+ * reward / importance_weight / effective_weight / partials / state pointer. */
+int rg_cb_eval_ingest_partials(int batch);
+int rg_cb_eval_ingest(const int64_t* action, const int64_t* model_action, const float* reward, const float* weight,
+                      const float* action_log_probability, const uint8_t* arm_presence, int batch, int arms,
+                      int clip, double max_importance_weight, float* importance_weight, float* effective_weight,
+                      double* partials, float* sum_weight_all_data, float* sum_reward_weighted_all_data,
+                      float* sum_size_weighted_all_data, float* sum_reward_importance_weighted_accepted,
+                      float* sum_reward_weighted_accepted, float* sum_weight_accepted,
+                      float* sum_importance_weight_accepted, float* sum_size_weighted_accepted,
+                      float* sum_weight_since_update, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -48,6 +48,10 @@ def _world_size() -> int:
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+def _refresh_dirty_after_load(module, incompatible_keys) -> None:
+    module.refresh_dirty()
+
+
 class UCBBaseModel(nn.Module):
     def __init__(self, input_dim: int):
         super().__init__()
@@ -94,17 +98,18 @@ class LinearRegressionUCB(UCBBaseModel):
         self.register_buffer("cur_sum_weight", 1e-5 * torch.ones(1, dtype=torch.float))
         self.dummy_param = nn.parameter.Parameter(torch.zeros(1))
         self._coefs_dirty = True  # (coefs_valid_for_avg_A = -1 != avg_A = 0: the reference's first forward calculates too)
+        # after ANY load that reaches this module -- its own load_state_dict or that of a module that holds it (a trainer, an
+        # evaluator's frozen copy): nested loads go through _load_from_state_dict and never call a load_state_dict override
+        self.register_load_state_dict_post_hook(_refresh_dirty_after_load)
 
     def mark_dirty(self) -> None:
         """the buffers moved: the next `coefs` / `forward` recalculates"""
         self._coefs_dirty = True
 
-    def load_state_dict(self, *args, **kwargs):
-        out = super().load_state_dict(*args, **kwargs)
-        # the reference's two comparisons (:202-204), once per load
+    def refresh_dirty(self) -> None:
+        """the reference's two comparisons (:202-204) on the buffers as they are, once per load"""
         self._coefs_dirty = bool(not (self.coefs_valid_for_avg_A == self.avg_A).all()
                                  or torch.abs(self.cur_avg_A).max().item() > 0)
-        return out
 
     def _calculate_coefs(self) -> None:
         """linear_regression.py:157-199 on a host copy: fold the epoch's averages into the all-data ones (reduce_avg, :54-89,

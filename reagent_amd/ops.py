@@ -787,6 +787,43 @@ def drlinucb_activate(a, b, act: int):
          lambda: L.lib().rg_drlinucb_activate(L.ptr(a), L.ptr(b), n, int(act), L.stream_ptr()))
 
 
+def cb_eval_partials(batch: int, device) -> torch.Tensor:
+    """the per-workgroup partial sums rg_cb_eval_ingest leaves for its finishing launch at `batch` rows (float64)"""
+    n = int(L.lib().rg_cb_eval_ingest_partials(int(batch)))
+    if n == 0:
+        raise L.ReagentHipError(f"rg_cb_eval_ingest does not take batch={batch} (batch >= 1)")
+    return torch.empty(8 * n, dtype=torch.float64, device=device)
+
+
+def cb_eval_ingest(action, model_action, reward, weight, action_log_probability, arm_presence, arms: int,
+                   max_importance_weight, importance_weight, effective_weight, partials, sums, sum_weight_since_update):
+    """BaseOfflineEval.ingest_batch on the device (see rg_cb_eval_ingest): importance_weight and effective_weight [B], and the
+    batch's sums added to `sums` (the eight one-element fp32 buffers, in the header's order) and to sum_weight_since_update.
+    weight, action_log_probability, arm_presence ([B, arms] uint8 or bool) and max_importance_weight may be None.  Two
+    launches, no synchronisation."""
+    m = _u8(arm_presence)
+    _chk_dev(action, model_action, reward, weight, action_log_probability, m, importance_weight, effective_weight, partials,
+             sum_weight_since_update, *sums)
+    B = action.numel()
+    for t in (action, model_action):
+        assert t.dtype == torch.int64 and t.is_contiguous() and t.numel() == B
+    for t in (reward, weight, action_log_probability, importance_weight, effective_weight):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.numel() == B)
+    assert m is None or (m.is_contiguous() and m.numel() == B * int(arms))
+    assert partials.dtype == torch.float64 and partials.is_contiguous()
+    assert partials.numel() >= 8 * int(L.lib().rg_cb_eval_ingest_partials(B))
+    assert len(sums) == 8
+    for t in (*sums, sum_weight_since_update):
+        assert t.dtype == F32 and t.numel() == 1
+    clip = max_importance_weight is not None
+    _run("rg_cb_eval_ingest", dict(B=B, arms=arms),
+         lambda: L.lib().rg_cb_eval_ingest(L.ptr(action), L.ptr(model_action), L.ptr(reward), L.ptr(weight),
+                                           L.ptr(action_log_probability), L.ptr(m), B, int(arms), int(clip),
+                                           float(max_importance_weight) if clip else 0.0, L.ptr(importance_weight),
+                                           L.ptr(effective_weight), L.ptr(partials), *[L.ptr(t) for t in sums],
+                                           L.ptr(sum_weight_since_update), L.stream_ptr()))
+
+
 def dlinucb_workspace(max_arm_rows: int, arms: int, dim: int, device) -> torch.Tensor:
     """the byte workspace rg_dlinucb_accumulate asks for at (max_arm_rows, arms, dim)"""
     n = int(L.lib().rg_dlinucb_workspace_bytes(int(max_arm_rows), int(arms), int(dim)))

@@ -14,7 +14,8 @@ label, its LinUCB layer updated by hand from the MLP's output.  One step, in the
 
 pred_sigma and ucb are NOT computed in the step: the reference computes them in the scorer's forward and discards them.
 `cb_training_step` returns the loss through the autograd bridge of training/plumbing.py (``loss.backward(); opt.step()``
-behave as under Lightning); `train_step_native` does the whole step without autograd and without a host synchronisation.
+behave as under Lightning); `train_step_native` does the whole step without autograd and without a host synchronisation.  With an evaluator attached
+(BaseCBTrainerWithEval) both paths run its frozen model and rg_cb_eval_ingest first and give the same bits.
 """
 import logging
 
@@ -99,8 +100,8 @@ class DeepRepresentLinUCBTrainer(NativeStepMixin, LinUCBTrainer):
                               loss=torch.empty(1, **f), dv=torch.empty(h + 1, **f))
         return self._bufs
 
-    def _forward(self, batch: CBInput, dv_into_slab: bool):
-        """solve, saving forward, head, accumulate.  dv_into_slab: the head writes d loss / d linear_layer.weight straight
+    def _forward(self, batch: CBInput, weight, dv_into_slab: bool):
+        """solve, saving forward, head, accumulate.  weight: the rows' weight [B, 1] or None.  dv_into_slab: the head writes d loss / d linear_layer.weight straight
         into the gradient slab (the native step); otherwise into a buffer the autograd bridge's backward copies from"""
         s = self.scorer
         if batch.features_of_chosen_arm is None:  # base_trainer.py:107 of the reference: training_step gathers them
@@ -115,10 +116,6 @@ class DeepRepresentLinUCBTrainer(NativeStepMixin, LinUCBTrainer):
         B = x.shape[0]
         label = self._f32c(batch.label).reshape(-1)
         assert label.numel() == B, f"Shapes of model prediction {(B,)} and label {tuple(batch.label.shape)} have to match"
-        # effective_weight (types.py:1194-1203) without the tensor of ones where no weight is given
-        weight = batch.weight
-        if batch.importance_weight is not None:
-            weight = batch.effective_weight
         if weight is not None:
             weight = self._f32c(weight).reshape(-1)
         net = self._engine()
@@ -156,8 +153,11 @@ class DeepRepresentLinUCBTrainer(NativeStepMixin, LinUCBTrainer):
 
     def cb_training_step(self, batch: CBInput, batch_idx: int, optimizer_idx: int = 0) -> torch.Tensor:
         refuse_disjoint(batch)
+        return self._step_with_weight(batch, self._row_weight(batch), batch_idx, optimizer_idx)
+
+    def _step_with_weight(self, batch: CBInput, weight, batch_idx: int, optimizer_idx: int = 0) -> torch.Tensor:
         with torch.no_grad():
-            w = self._forward(batch, dv_into_slab=False)
+            w = self._forward(batch, weight, dv_into_slab=False)
         return self._net.loss(self._backward_bridge, w["loss"])
 
     @torch.no_grad()
@@ -166,14 +166,18 @@ class DeepRepresentLinUCBTrainer(NativeStepMixin, LinUCBTrainer):
         """the whole step -- solve, forward, head, accumulate, backward, Adam -- with no autograd graph and no host
         synchronisation; returns the loss [1] on the device"""
         refuse_disjoint(batch)
-        if self.eval_module is not None:
-            raise NotImplementedError("an attached eval_module (offline evaluation inside the training loop) is not "
-                                      "implemented")
-        self._check_input(batch, offline_eval=False)
+        evaluated = self.eval_module is not None
+        if evaluated:
+            self._check_eval_module(self.eval_module)
+        self._check_input(batch, offline_eval=evaluated)
         (opt,) = self.native_optimizers()
+        if evaluated:  # (before the step touches the scorer: the frozen model may have to be replaced by a copy of it)
+            batch, weight = self._evaluate(batch)
+        else:
+            weight = self._row_weight(batch)
         net = self._engine()
         net.clear_grads()
-        w = self._forward(batch, dv_into_slab=True)
+        w = self._forward(batch, weight, dv_into_slab=True)
         self._native_segment(net, lambda: self._backward(), opt)
         self.all_batches_processed += 1
         return w["loss"]

@@ -54,11 +54,10 @@ class LinUCBTrainer(BaseCBTrainerWithEval):
         self._accumulate(x, y, weight)
 
     def cb_training_step(self, batch: CBInput, batch_idx: int, optimizer_idx: int = 0) -> Optional[torch.Tensor]:
+        return self._step_with_weight(batch, self._row_weight(batch), batch_idx, optimizer_idx)
+
+    def _step_with_weight(self, batch: CBInput, weight, batch_idx: int, optimizer_idx: int = 0) -> Optional[torch.Tensor]:
         assert batch.label is not None
-        # effective_weight (types.py:1194-1203) without the tensor of ones where no weight is given
-        weight = batch.weight
-        if batch.importance_weight is not None:
-            weight = batch.effective_weight
         if batch.features_of_chosen_arm is not None:
             self._accumulate(batch.features_of_chosen_arm, batch.label, weight)
         else:  # [B, A, d] and the logged action, straight to the kernel

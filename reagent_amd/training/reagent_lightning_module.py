@@ -34,6 +34,7 @@ class ReAgentLightningModule(nn.Module):
         self._reporter = _NoOpReporter()
         self._verified_steps = False
         self.logger = None
+        self.global_step = 0  # LightningModule.global_step: the step handed to a logger (a loop that counts steps sets it)
         self.register_buffer("_next_stopping_epoch", None)
         self.register_buffer("_cleanly_stopped", None)
         self._next_stopping_epoch = torch.tensor([-1]).int()
