@@ -3,9 +3,12 @@
 // acting is the GEMM x * inv_avg_A fused with the row dot that turns it into x^T inv_avg_A x, the mean x * coefs, the
 // upper confidence bound and a masked arg-max over each row's arms.  Both products run on the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation).  No atomics: partials leave per workgroup and a
-// finishing launch adds them in a fixed order, so two runs give the same bits.
+// finishing launch adds them in a fixed order, so two runs give the same bits.  The accumulate path's body is rg_cb.h's,
+// shared with cb_disjoint.hip; this file keeps the plan (how the batch is cut into slices) and the running average.
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
+#include "rg_cb.h"      // the Gram tile body, the finishing sum, the tile numbering, the arg-max rule
+#include "rg_reduce.h"  // lds_tree_sum
 
 // The running-average update is held to the reference's fp32 operation order: every multiply, divide, subtract and add is
 // rounded on its own (hipcc would otherwise contract a * b + c into one fused multiply-add).
@@ -13,11 +16,9 @@
 
 namespace rg {
 
-constexpr int CB_THREADS = 256;
-constexpr int CB_WAVES = CB_THREADS / 64;
-constexpr int CB_TILE = 32;             // the MFMA's 32 x 32 output tile
 constexpr int CB_SLICE_MIN_ROWS = 256;  // a workgroup's slice of the batch is at least this long (64 rows a wave) ...
 constexpr int CB_MAX_BLOCKS = 1024;     // ... and the launch has about this many workgroups at the most
+constexpr int CB_UNROLL = 4;            // MFMA steps whose operands are loaded together (cb_gram_tile)
 
 struct CbPlan {
   int tiles_1d, tiles, slices, slice_rows;
@@ -26,8 +27,8 @@ struct CbPlan {
 // the same plan for rg_linucb_workspace_bytes and rg_linucb_accumulate: a function of (B, d) alone
 static CbPlan cb_plan(int B, int d) {
   CbPlan p;
-  p.tiles_1d = (d + CB_TILE - 1) / CB_TILE;
-  p.tiles = p.tiles_1d * (p.tiles_1d + 1) / 2;  // tiles on or above the diagonal
+  p.tiles_1d = cb_tiles_1d(d);
+  p.tiles = cb_tiles(p.tiles_1d);
   int slices = (B + CB_SLICE_MIN_ROWS - 1) / CB_SLICE_MIN_ROWS;
   const int cap = CB_MAX_BLOCKS / p.tiles > 1 ? CB_MAX_BLOCKS / p.tiles : 1;
   slices = slices < cap ? slices : cap;
@@ -44,96 +45,36 @@ struct CbWorkspace {
   float *gram, *sb, *sw, *old_sw;
 };
 static size_t cb_workspace_floats(const CbPlan& p) {
-  return (size_t)p.slices * p.tiles * (CB_TILE * CB_TILE) + (size_t)p.slices * p.tiles_1d * CB_TILE + p.slices + 1;
+  return (size_t)p.slices * p.tiles * CB_TILE_ELEMS + (size_t)p.slices * p.tiles_1d * CB_TILE + p.slices + 1;
 }
 static CbWorkspace cb_carve(const CbPlan& p, void* workspace) {
   CbWorkspace w;
   w.gram = (float*)workspace;
-  w.sb = w.gram + (size_t)p.slices * p.tiles * (CB_TILE * CB_TILE);
+  w.sb = w.gram + (size_t)p.slices * p.tiles * CB_TILE_ELEMS;
   w.sw = w.sb + (size_t)p.slices * p.tiles_1d * CB_TILE;
   w.old_sw = w.sw + p.slices;
   return w;
 }
 
 struct CbAccArgs {
-  const float* x;         // [B, d], or [B, A, d] with action
-  const int64_t* action;  // [B] or NULL
-  const float *y, *weight;
+  CbRows rows;  // x [B, d], or [B, A, d] with action
   const float* cur_sum_weight;
-  int B, d, arms, tiles_1d, slice_rows;
+  int B, d, tiles_1d, slice_rows;
   CbWorkspace ws;
 };
 
-// Workgroup (t, s): tile t = (ti, tj), ti <= tj, of the Gram matrix over the rows of slice s.  Each wave walks its share of
-// the slice two rows a step (rows 2 * wave + 8 * step + {0, 1}): lane l holds row k = l >> 5 of the step and column l & 31
-// of both tiles, A[i][k] = w_k * x[k][32 ti + i] and B[k][j] = x[k][32 tj + j] in the fragment maps of rg_platform.h, read
-// straight from global memory (128 contiguous bytes per half wave).  The diagonal workgroups add S_b's partial from the
-// registers they hold anyway, and workgroup (0, s) the slice's sum of weights.  The four waves' tiles meet in LDS and are
-// added in wave order.
+// Workgroup (t, s): tile t of the Gram matrix over the rows of slice s of the batch (cb_gram_tile).  Workgroup (0, s) also
+// leaves the slice's sum of weights.
 __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_gram_kernel(const CbAccArgs a) {
-  __shared__ float tile[CB_WAVES][CB_TILE * CB_TILE];
-  __shared__ float vec[CB_WAVES][64];
-  __shared__ float wsum[CB_WAVES][2];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int t = blockIdx.x, s = blockIdx.y;
-  int ti = 0, first = 0;  // tiles are numbered row by row over the upper triangle
-  while (t >= first + (a.tiles_1d - ti)) first += a.tiles_1d - ti, ++ti;
-  const int tj = ti + (t - first);
-  const int col = lane & 31, half = lane >> 5;
-  const int ca = ti * CB_TILE + col, cb = tj * CB_TILE + col;
-  const bool ca_ok = ca < a.d, cb_ok = cb < a.d;
+  int ti, tj;
+  cb_tile_of(t, a.tiles_1d, ti, tj);
   const long row_begin = (long)s * a.slice_rows;
   const long row_end = row_begin + a.slice_rows < a.B ? row_begin + a.slice_rows : a.B;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float sb = 0.f, sw = 0.f;
-  for (long r0 = row_begin + 2 * wave; r0 < row_end; r0 += 2 * CB_WAVES) {  // (wave-uniform trip count)
-    const long row = r0 + half;
-    const bool live = row < row_end;
-    float w = 0.f, wy = 0.f, xa = 0.f, xb = 0.f;
-    if (live) {
-      long src = row;
-      if (a.action) {  // the chosen arm's row, read in place; the index clamped into [0, arms)
-        long arm = a.action[row];
-        arm = arm < 0 ? 0 : (arm >= a.arms ? a.arms - 1 : arm);
-        src = row * a.arms + arm;
-      }
-      w = a.weight ? a.weight[row] : 1.f;
-      wy = w * a.y[row];
-      const float* xr = a.x + src * a.d;
-      xa = ca_ok ? xr[ca] : 0.f;
-      xb = cb_ok ? xr[cb] : 0.f;
-    }
-    acc = mfma_32x32x2_f32(w * xa, xb, acc);
-    sb += wy * xa;
-    sw += w;
-  }
-  float* mine = tile[wave];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-    mine[i * CB_TILE + col] = acc[r];
-  }
-  vec[wave][lane] = sb;
-  if (col == 0) wsum[wave][half] = sw;
-  __syncthreads();
-  float* out = a.ws.gram + ((size_t)s * gridDim.x + t) * (CB_TILE * CB_TILE);
-  for (int e = threadIdx.x; e < CB_TILE * CB_TILE; e += CB_THREADS)
-    out[e] = ((tile[0][e] + tile[1][e]) + tile[2][e]) + tile[3][e];
-  if (ti == tj && threadIdx.x < CB_TILE) {
-    float v = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < CB_WAVES; ++wv) v = (v + vec[wv][threadIdx.x]) + vec[wv][threadIdx.x + 32];
-    a.ws.sb[((size_t)s * a.tiles_1d + ti) * CB_TILE + threadIdx.x] = v;
-  }
-  if (t == 0 && threadIdx.x == 0) {
-    float v = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < CB_WAVES; ++wv) v = (v + wsum[wv][0]) + wsum[wv][1];
-    a.ws.sw[s] = v;
-    if (s == 0) *a.ws.old_sw = *a.cur_sum_weight;
-  }
+  cb_gram_tile<CB_UNROLL, true>(a.rows, row_begin, row_end, a.d, ti, tj,
+                                a.ws.gram + ((size_t)s * gridDim.x + t) * CB_TILE_ELEMS,
+                                a.ws.sb + ((size_t)s * a.tiles_1d + ti) * CB_TILE, t == 0 ? a.ws.sw + s : nullptr);
+  if (t == 0 && s == 0 && threadIdx.x == 0) *a.ws.old_sw = *a.cur_sum_weight;
 }
 
 struct CbFinishArgs {
@@ -143,14 +84,12 @@ struct CbFinishArgs {
   int B, d, tiles_1d, tiles, slices;
 };
 
-// linucb_trainer.py:64-75 in its fp32 operation order, on the ordered sums of the partials.  One thread per entry on or
-// above the diagonal (it writes the mirrored entry too: an exactly symmetric matrix whatever was there) and, past those,
-// one per entry of cur_avg_b.  Every thread reads the sum of weights the MAIN launch saw from the workspace; thread 0
-// alone rewrites cur_sum_weight and cur_num_obs.
+// linucb_trainer.py:64-75 in its fp32 operation order, on the ordered sums of the partials: one thread per entry
+// (cb_finish_entry).  Every thread reads the sum of weights the MAIN launch saw from the workspace; thread 0 alone
+// rewrites cur_sum_weight and cur_num_obs.
 __global__ void linucb_finish_kernel(const CbFinishArgs a) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  const long dd = (long)a.d * a.d;
-  if (e >= dd + a.d) return;
+  if (e >= (long)a.d * a.d + a.d) return;
   float batch_sw = 0.f;
   for (int s = 0; s < a.slices; ++s) batch_sw += a.ws.sw[s];
   const float sum_w = *a.ws.old_sw + batch_sw;                    // cur_sum_weight += batch_sum_weight
@@ -159,23 +98,12 @@ __global__ void linucb_finish_kernel(const CbFinishArgs a) {
     *a.cur_sum_weight = sum_w;
     *a.cur_num_obs += (int64_t)a.B;                               // cur_num_obs += y.shape[0]
   }
-  if (e < dd) {
-    const int i = (int)(e / a.d), j = (int)(e % a.d);
-    if (i > j) return;
-    const int ti = i / CB_TILE, tj = j / CB_TILE;
-    const int t = ti * a.tiles_1d - ti * (ti - 1) / 2 + (tj - ti);
-    const size_t off = (size_t)t * (CB_TILE * CB_TILE) + (i % CB_TILE) * CB_TILE + (j % CB_TILE);
-    float S = 0.f;
-    for (int s = 0; s < a.slices; ++s) S += a.ws.gram[(size_t)s * a.tiles * (CB_TILE * CB_TILE) + off];
-    const float v = a.cur_avg_A[e] * keep + S / sum_w;
-    a.cur_avg_A[e] = v;
-    a.cur_avg_A[(long)j * a.d + i] = v;
-  } else {
-    const int i = (int)(e - dd);
-    float S = 0.f;
-    for (int s = 0; s < a.slices; ++s) S += a.ws.sb[(size_t)s * a.tiles_1d * CB_TILE + i];
-    a.cur_avg_b[i] = a.cur_avg_b[i] * keep + S / sum_w;
-  }
+  const CbEntry en = cb_finish_entry(e, a.d, a.tiles_1d, a.tiles, a.slices, a.ws.gram, a.ws.sb);
+  if (en.below) return;
+  float* out = en.in_A ? a.cur_avg_A : a.cur_avg_b;
+  const float v = out[en.at] * keep + en.S / sum_w;
+  out[en.at] = v;
+  out[en.mirror] = v;
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------
@@ -243,7 +171,7 @@ __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_score_kernel(const CbScor
   const int col = lane & 31, half = lane >> 5;
   const long row0 = (long)blockIdx.x * CB_SCORE_ROWS;
   const int d = a.d;
-  const int tiles_1d = (d + CB_TILE - 1) / CB_TILE;
+  const int tiles_1d = cb_tiles_1d(d);
   const bool with_sigma = a.alpha != 0.f;
   f32x16 acc[CB_SCORE_TILES];
 #pragma unroll
@@ -287,7 +215,7 @@ __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_score_kernel(const CbScor
         const int j = tj * CB_TILE + col;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const long row = row0 + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const long row = row0 + cb_acc_row(r, half);
           const float xv = (row < a.N && j < d) ? a.x[row * d + j] : 0.f;
           part[r] += acc[q][r] * xv;
         }
@@ -295,13 +223,8 @@ __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_score_kernel(const CbScor
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      float v = part[r];
-      v += shfl_xor(v, 1);
-      v += shfl_xor(v, 2);
-      v += shfl_xor(v, 4);
-      v += shfl_xor(v, 8);
-      v += shfl_xor(v, 16);
-      if (col == 0) qpart[wave][(r & 3) + 8 * (r >> 2) + 4 * half] = v;
+      const float v = cb_half_wave_sum(part[r]);
+      if (col == 0) qpart[wave][cb_acc_row(r, half)] = v;
     }
   }
   __syncthreads();
@@ -330,8 +253,7 @@ __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_score_kernel(const CbScor
 }
 
 // The finishing launch of rg_linucb_score: workgroup 0 adds the per-workgroup NaN counts in order into nan_count[0]; every
-// thread takes one batch row and walks its arms for the arg-max of ucb under arm_presence, the lowest index among equals
-// (torch.argmax), a NaN before any number (torch.argmax again), arm 0 where no arm is present.
+// thread takes one batch row and walks its arms for the arg-max of ucb under arm_presence by CbBest's rule.
 __global__ void linucb_select_kernel(const float* __restrict__ ucb, const uint8_t* __restrict__ arm_presence, int B,
                                      int arms, const int32_t* __restrict__ nan_partials, int partials,
                                      int32_t* __restrict__ nan_count, int64_t* __restrict__ best_arm) {
@@ -340,25 +262,15 @@ __global__ void linucb_select_kernel(const float* __restrict__ ucb, const uint8_
     int n = 0;
     for (int p = threadIdx.x; p < partials; p += CB_THREADS) n += nan_partials[p];
     counts[threadIdx.x] = n;
-    __syncthreads();
-    for (int off = CB_THREADS / 2; off >= 1; off >>= 1) {
-      if ((int)threadIdx.x < off) counts[threadIdx.x] += counts[threadIdx.x + off];
-      __syncthreads();
-    }
+    lds_tree_sum<CB_THREADS>(counts);
     if (threadIdx.x == 0) *nan_count = counts[0];
   }
   const long b = (long)blockIdx.x * CB_THREADS + threadIdx.x;
   if (arms < 1 || b >= B) return;
-  float best = -INFINITY;
-  int best_a = 0;
-  bool found = false;
-  for (int k = 0; k < arms; ++k) {
-    if (arm_presence && !arm_presence[b * arms + k]) continue;
-    const float v = ucb[b * arms + k];
-    if (!found || v != v || v > best) best = v, best_a = k, found = true;
-    if (v != v) break;
-  }
-  best_arm[b] = best_a;
+  CbBest best;
+  for (int k = 0; k < arms && !best.closed; ++k)
+    best.take(ucb[b * arms + k], k, !arm_presence || arm_presence[b * arms + k]);
+  best_arm[b] = best.arm;
 }
 
 }  // namespace rg
@@ -381,8 +293,8 @@ int rg_linucb_accumulate(const float* x, const int64_t* action, int arms, const 
   const CbPlan p = cb_plan(batch, dim);
   if (workspace_bytes < cb_workspace_floats(p) * sizeof(float)) return RG_EINVAL;
   CbAccArgs a;
-  a.x = x, a.action = action, a.y = y, a.weight = weight, a.cur_sum_weight = cur_sum_weight;
-  a.B = batch, a.d = dim, a.arms = action ? arms : 1, a.tiles_1d = p.tiles_1d, a.slice_rows = p.slice_rows;
+  a.rows.x = x, a.rows.y = y, a.rows.weight = weight, a.rows.action = action, a.rows.arms = action ? arms : 1;
+  a.cur_sum_weight = cur_sum_weight, a.B = batch, a.d = dim, a.tiles_1d = p.tiles_1d, a.slice_rows = p.slice_rows;
   a.ws = cb_carve(p, workspace);
   RG_LAUNCH(linucb_gram_kernel, dim3(p.tiles, p.slices), dim3(CB_THREADS), (hipStream_t)stream, a);
   CbFinishArgs f;

@@ -3,10 +3,12 @@
 // matrix in registers) and the loss head behind the MLP (ones column, mean through linear_layer or the coefficients, output
 // activation, weighted mse / mae / binary cross-entropy, the gradients into the MLP's output and linear_layer.weight).
 // No atomics: partials leave per workgroup and a finishing launch adds them in a fixed order, so two runs give the same
-// bits.
+// bits.  The launch constants are rg_cb.h's, the fp64 wave sum and the LDS tree rg_reduce.h's.
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
-#include "rg_gemm.h"  // act_apply / act_grad_from_output: the FC epilogues' activation functions
+#include "rg_cb.h"      // CB_THREADS, CB_WAVES: the bandit kernels' launch shape
+#include "rg_gemm.h"    // act_apply / act_grad_from_output: the FC epilogues' activation functions
+#include "rg_reduce.h"  // wave_sum_f64, lds_tree_sum
 
 // The fold is held to the reference's fp32 operation order: every multiply, divide and add is rounded on its own.  Where a
 // fused multiply-add is wanted (the elimination, the dots) it is written out as fmaf.
@@ -14,13 +16,10 @@
 
 namespace rg {
 
-constexpr int DCB_THREADS = 256;
-constexpr int DCB_WAVES = DCB_THREADS / 64;
-
 // ---- rg_linucb_solve ----------------------------------------------------------------------------------------------------
 constexpr int SOLVE_SIDE = 16;                                     // the workgroup is a 16 x 16 grid of threads
 constexpr int SOLVE_PER = RG_LINUCB_SOLVE_MAX_DIM / SOLVE_SIDE;    // each holds 8 x 8 entries: (ty + 16 a, tx + 16 b)
-static_assert(SOLVE_SIDE * SOLVE_SIDE == DCB_THREADS && SOLVE_PER * SOLVE_SIDE == RG_LINUCB_SOLVE_MAX_DIM, "solve layout");
+static_assert(SOLVE_SIDE * SOLVE_SIDE == CB_THREADS && SOLVE_PER * SOLVE_SIDE == RG_LINUCB_SOLVE_MAX_DIM, "solve layout");
 
 struct SolveArgs {
   int d;
@@ -44,7 +43,7 @@ struct SolveArgs {
 // step k + 1, behind which every thread has finished reading step k's values.  The trip counts depend on d alone: a
 // non-positive or non-finite pivot p raises the flag and the arithmetic goes on (infinities and NaNs, no loop on data).
 template <int NB>
-__global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) linucb_solve_kernel(const SolveArgs a) {
+__global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) linucb_solve_kernel(const SolveArgs a) {
   __shared__ float rowk[2][RG_LINUCB_SOLVE_MAX_DIM], colk[2][RG_LINUCB_SOLVE_MAX_DIM];
   __shared__ float bvec[RG_LINUCB_SOLVE_MAX_DIM];
   const int t = threadIdx.x, tx = t & (SOLVE_SIDE - 1), ty = t >> 4;
@@ -166,30 +165,16 @@ struct DrHeadArgs {
   float *loss_partials, *dv_partials;
 };
 
-__device__ __forceinline__ double drh_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    long long b;
-    memcpy(&b, &v, 8);
-    const int lo = shfl_xor((int)b, off), hi = shfl_xor((int)(b >> 32), off);
-    b = ((long long)hi << 32) | (long long)(unsigned)lo;
-    double o;
-    memcpy(&o, &b, 8);
-    v += o;
-  }
-  return v;
-}
-
 // A group of G lanes per row, 256 / G rows a pass, block_rows rows a workgroup.  Lane g of the group walks the columns
 // g, g + G, ... of mlp_out (coalesced), copies them behind the ones column of z and adds up its share of z . v; the
 // group's sum by butterflies is the same bits in each of its lanes.  Every lane then forms the row's prediction, loss and
 // d loss / d lin and writes its columns of d loss / d mlp_out = dlin * v[1:].  dlin of the workgroup's rows meets in LDS:
 // thread c owns column c of the dv partial and adds dlin_r * z_r[c] over the rows in order (z_r[c] read from mlp_out).
 template <int G>
-__global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) drlinucb_head_kernel(const DrHeadArgs a) {
-  __shared__ float sdlin[DCB_THREADS];
-  __shared__ double scratch[DCB_WAVES];
-  constexpr int ROWS = DCB_THREADS / G;
+__global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) drlinucb_head_kernel(const DrHeadArgs a) {
+  __shared__ float sdlin[CB_THREADS];
+  __shared__ double scratch[CB_WAVES];
+  constexpr int ROWS = CB_THREADS / G;
   const int g = threadIdx.x & (G - 1), rl = threadIdx.x / G;
   const int h = a.h, d = h + 1;
   const long row0 = (long)blockIdx.x * a.block_rows;
@@ -246,14 +231,14 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) drlinucb_head_kernel(const DrHe
     if (g == 0) sdlin[r0 + rl] = live ? dlin : 0.f;
   }
   if (!train) return;
-  loss_acc = drh_wave_sum_f64(loss_acc);
+  loss_acc = wave_sum_f64(loss_acc);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = loss_acc;
   __syncthreads();  // (also: sdlin is complete)
   if (threadIdx.x == 0) a.loss_partials[blockIdx.x] = (float)((scratch[0] + scratch[1]) + (scratch[2] + scratch[3]));
   if (!a.dv_partials) return;
   const long left = a.B - row0;
   const int nrows = left < a.block_rows ? (int)left : a.block_rows;
-  for (int c = threadIdx.x; c < d; c += DCB_THREADS) {
+  for (int c = threadIdx.x; c < d; c += CB_THREADS) {
     float s = 0.f;
     for (int r = 0; r < nrows; ++r) {
       const float zc = c == 0 ? 1.f : a.mlp[(row0 + r) * a.ld + (c - 1)];
@@ -265,20 +250,16 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) drlinucb_head_kernel(const DrHe
 
 // The finishing launch: workgroup 0 the loss, workgroup 1 + c column c of dv.  Thread t adds the partials t, t + 256, ...
 // in double, the 256 sums meet in LDS by a fixed tree.
-__global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) drlinucb_finish_kernel(const float* __restrict__ loss_partials,
+__global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) drlinucb_finish_kernel(const float* __restrict__ loss_partials,
                                                                          const float* __restrict__ dv_partials, int P, int d,
                                                                          int B, float* __restrict__ loss,
                                                                          float* __restrict__ dv) {
-  __shared__ double sums[DCB_THREADS];
+  __shared__ double sums[CB_THREADS];
   const int c = (int)blockIdx.x - 1;
   double s = 0.0;
-  for (int p = threadIdx.x; p < P; p += DCB_THREADS) s += (double)(c < 0 ? loss_partials[p] : dv_partials[(long)p * d + c]);
+  for (int p = threadIdx.x; p < P; p += CB_THREADS) s += (double)(c < 0 ? loss_partials[p] : dv_partials[(long)p * d + c]);
   sums[threadIdx.x] = s;
-  __syncthreads();
-  for (int off = DCB_THREADS / 2; off >= 1; off >>= 1) {
-    if ((int)threadIdx.x < off) sums[threadIdx.x] += sums[threadIdx.x + off];
-    __syncthreads();
-  }
+  lds_tree_sum<CB_THREADS>(sums);
   if (threadIdx.x == 0) {
     if (c < 0) *loss = (float)(sums[0] / (double)B);
     else dv[c] = (float)sums[0];
@@ -286,7 +267,7 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) drlinucb_finish_kernel(const fl
 }
 
 __global__ void drlinucb_activate_kernel(float* __restrict__ x, float* __restrict__ y, int n, int act) {
-  const long i = (long)blockIdx.x * DCB_THREADS + threadIdx.x;
+  const long i = (long)blockIdx.x * CB_THREADS + threadIdx.x;
   if (i >= n) return;
   x[i] = act_apply(x[i], act);
   if (y) y[i] = act_apply(y[i], act);
@@ -294,7 +275,7 @@ __global__ void drlinucb_activate_kernel(float* __restrict__ x, float* __restric
 
 static int drh_group(int h) { return h <= 4 ? 1 : (h <= 16 ? 4 : (h <= 64 ? 16 : 64)); }
 static int drh_block_rows(int h) {
-  const int rows = DCB_THREADS / drh_group(h);
+  const int rows = CB_THREADS / drh_group(h);
   return rows > DRH_MIN_BLOCK_ROWS ? rows : DRH_MIN_BLOCK_ROWS;
 }
 static bool drh_act_ok(int act) { return act >= RG_ACT_LINEAR && act <= RG_ACT_SOFTPLUS; }
@@ -317,7 +298,7 @@ int rg_linucb_solve(int dim, double l2_reg_lambda, float* avg_A, float* avg_b, f
   a.avg_A = avg_A, a.avg_b = avg_b, a.sum_weight = sum_weight, a.num_obs = num_obs;
   a.cur_avg_A = cur_avg_A, a.cur_avg_b = cur_avg_b, a.cur_sum_weight = cur_sum_weight, a.cur_num_obs = cur_num_obs;
   a.inv_avg_A = inv_avg_A, a.coefs = coefs, a.valid = coefs_valid_for_avg_A, a.status = status;
-  const dim3 grid(1), block(DCB_THREADS);
+  const dim3 grid(1), block(CB_THREADS);
   if (dim <= 16) RG_LAUNCH(linucb_solve_kernel<1>, grid, block, (hipStream_t)stream, a);
   else if (dim <= 32) RG_LAUNCH(linucb_solve_kernel<2>, grid, block, (hipStream_t)stream, a);
   else if (dim <= 64) RG_LAUNCH(linucb_solve_kernel<4>, grid, block, (hipStream_t)stream, a);
@@ -349,7 +330,7 @@ int rg_drlinucb_head(const float* mlp_out, int64_t ld_mlp_out, const float* v, c
   a.z = z, a.lin = lin, a.pred = pred_label, a.row_loss = row_loss, a.dmlp = dmlp_out, a.ld_dmlp = (long)ld_dmlp_out;
   a.loss_partials = loss_partials, a.dv_partials = (label && dv) ? dv_partials : nullptr;
   const int P = rg_drlinucb_head_partials(batch, h);
-  const dim3 grid(P), block(DCB_THREADS);
+  const dim3 grid(P), block(CB_THREADS);
   switch (drh_group(h)) {
     case 1: RG_LAUNCH(drlinucb_head_kernel<1>, grid, block, (hipStream_t)stream, a); break;
     case 4: RG_LAUNCH(drlinucb_head_kernel<4>, grid, block, (hipStream_t)stream, a); break;
@@ -364,7 +345,7 @@ int rg_drlinucb_head(const float* mlp_out, int64_t ld_mlp_out, const float* v, c
 
 int rg_drlinucb_activate(float* a, float* b, int n, int act, rg_stream_t stream) {
   if (n < 1 || !a || !drh_act_ok(act)) return RG_EINVAL;
-  RG_LAUNCH(drlinucb_activate_kernel, dim3((n + DCB_THREADS - 1) / DCB_THREADS), dim3(DCB_THREADS), (hipStream_t)stream, a, b,
+  RG_LAUNCH(drlinucb_activate_kernel, dim3((n + CB_THREADS - 1) / CB_THREADS), dim3(CB_THREADS), (hipStream_t)stream, a, b,
             n, act);
   return (int)hipGetLastError();
 }

@@ -2,18 +2,17 @@
 // updates over the arms' sub-batches, which lie back to back in one packed batch (row_offsets, in device memory, says where
 // each begins); acting scores every row against every arm's own inverse.  Both products run on the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32: exact fp32 products, fp32 accumulation).  No atomics: partials leave per workgroup and are added
-// in a fixed order, so two runs give the same bits.
+// in a fixed order, so two runs give the same bits.  The accumulate path's body is rg_cb.h's, shared with cb.hip; this file
+// keeps the plan (how an arm's rows are cut into slices) and the plain add.
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
+#include "rg_cb.h"  // the Gram tile body, the finishing sum, the tile numbering, the arg-max rule (shared with cb.hip)
 
 // every multiply and add is rounded on its own (ucb = mean + alpha * sigma is one multiply and one add; cur_A += S one add)
 #pragma clang fp contract(off)
 
 namespace rg {
 
-constexpr int DCB_THREADS = 256;
-constexpr int DCB_WAVES = DCB_THREADS / 64;
-constexpr int DCB_TILE = 32;               // the MFMA's 32 x 32 output tile
 constexpr int DCB_SLICE_UNIT = 256;        // a slice is 1 .. 8 units of rows, by the number of tiles (a function of d alone)
 constexpr int DCB_MAX_BLOCKS = 1 << 20;    // workgroups of the main launch at the most
 constexpr int DCB_MAX_ARMS = 65535;        // (a grid dimension)
@@ -28,8 +27,8 @@ struct DcbPlan {
 // call and in a call of its own.  The hint only says how many slices the grid has; the last one runs to the arm's end.
 static DcbPlan dcb_plan(int max_arm_rows, int arms, int d) {
   DcbPlan p;
-  p.tiles_1d = (d + DCB_TILE - 1) / DCB_TILE;
-  p.tiles = p.tiles_1d * (p.tiles_1d + 1) / 2;  // tiles on or above the diagonal
+  p.tiles_1d = cb_tiles_1d(d);
+  p.tiles = cb_tiles(p.tiles_1d);
   int units = p.tiles / 4;
   units = units < 1 ? 1 : (units > 8 ? 8 : units);
   p.slice_rows = DCB_SLICE_UNIT * units;
@@ -41,11 +40,9 @@ static DcbPlan dcb_plan(int max_arm_rows, int arms, int d) {
 }
 
 // workspace layout (floats): [arms][slices][tiles][32 * 32] Gram partials, then [arms][slices][tiles_1d * 32] S_b partials
-static size_t dcb_gram_floats(const DcbPlan& p, int arms) {
-  return (size_t)arms * p.slices * p.tiles * (DCB_TILE * DCB_TILE);
-}
+static size_t dcb_gram_floats(const DcbPlan& p, int arms) { return (size_t)arms * p.slices * p.tiles * CB_TILE_ELEMS; }
 static size_t dcb_workspace_floats(const DcbPlan& p, int arms) {
-  return dcb_gram_floats(p, arms) + (size_t)arms * p.slices * p.tiles_1d * DCB_TILE;
+  return dcb_gram_floats(p, arms) + (size_t)arms * p.slices * p.tiles_1d * CB_TILE;
 }
 
 struct DcbAccArgs {
@@ -65,84 +62,26 @@ __device__ __forceinline__ void dcb_arm_rows(const DcbAccArgs& a, int arm, long&
   begin = b, end = e;
 }
 
-// Workgroup (s, t, arm): tile t = (ti, tj), ti <= tj, of arm's Gram matrix over slice s of ITS rows (counted from the arm's
-// first row: nothing depends on where the arm lies in the packed batch).  Each wave walks its share of the slice two rows a
-// step (rows 2 * wave + 8 * step + {0, 1}): lane l holds row k = l >> 5 of the step and column l & 31 of both tiles,
-// A[i][k] = w_k * x[k][32 ti + i] and B[k][j] = x[k][32 tj + j], read straight from global memory (128 contiguous bytes per
-// half wave), DCB_UNROLL steps' operands together from addresses clamped into the slice (no branch around a load).  The
-// diagonal workgroups add S_b's partial from the registers they hold anyway.  The four waves' tiles meet in LDS and are
-// added in wave order.  An empty slice writes zero partials.
-__global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_gram_kernel(const DcbAccArgs a) {
-  __shared__ float tile[DCB_WAVES][DCB_TILE * DCB_TILE];
-  __shared__ float vec[DCB_WAVES][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+// Workgroup (s, t, arm): tile t of arm's Gram matrix over slice s of ITS rows, counted from the arm's first row: nothing
+// depends on where the arm lies in the packed batch (cb_gram_tile).  An empty slice writes zero partials.
+__global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) dlinucb_gram_kernel(const DcbAccArgs a) {
   const int s = blockIdx.x, t = blockIdx.y, arm = blockIdx.z;
-  int ti = 0, first = 0;  // tiles are numbered row by row over the upper triangle
-  while (t >= first + (a.tiles_1d - ti)) first += a.tiles_1d - ti, ++ti;
-  const int tj = ti + (t - first);
-  const int col = lane & 31, half = lane >> 5;
-  const int ca = ti * DCB_TILE + col, cb = tj * DCB_TILE + col;
-  const bool ca_ok = ca < a.d, cb_ok = cb < a.d;
-  const int cac = ca_ok ? ca : a.d - 1, cbc = cb_ok ? cb : a.d - 1;
+  int ti, tj;
+  cb_tile_of(t, a.tiles_1d, ti, tj);
   long begin, end;
   dcb_arm_rows(a, arm, begin, end);
   long row_begin = begin + (long)s * a.slice_rows;
   row_begin = row_begin < end ? row_begin : end;
   long row_end = row_begin + a.slice_rows < end ? row_begin + a.slice_rows : end;
   if (s == a.slices - 1) row_end = end;  // the hint sizes the grid; it never decides which rows count
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  float sb = 0.f;
-  for (long r0 = row_begin + 2 * wave; r0 < row_end; r0 += 2 * DCB_WAVES * DCB_UNROLL) {  // (wave-uniform trip count)
-    float wv[DCB_UNROLL], yv[DCB_UNROLL], xa[DCB_UNROLL], xb[DCB_UNROLL];
-    bool live[DCB_UNROLL];
-#pragma unroll
-    for (int u = 0; u < DCB_UNROLL; ++u) {
-      const long row = r0 + 2 * DCB_WAVES * u + half;
-      live[u] = row < row_end;
-      const long rc = live[u] ? row : row_end - 1;  // (row_begin <= r0 <= row_end - 1: a row of this slice)
-      wv[u] = a.weight ? a.weight[rc] : 1.f;
-      yv[u] = a.y[rc];
-      xa[u] = a.x[rc * a.d + cac];
-      xb[u] = a.x[rc * a.d + cbc];
-    }
-#pragma unroll
-    for (int u = 0; u < DCB_UNROLL; ++u) {
-      // (uniform over the wave: the steps past the slice's end are skipped whole, a half step has its dead row zeroed)
-      if (r0 + 2 * DCB_WAVES * u < row_end) {
-        const float w = live[u] ? wv[u] : 0.f;
-        const float va = (live[u] && ca_ok) ? xa[u] : 0.f;
-        const float vb = (live[u] && cb_ok) ? xb[u] : 0.f;
-        const float wy = w * (live[u] ? yv[u] : 0.f);
-        acc = mfma_32x32x2_f32(w * va, vb, acc);
-        sb += wy * va;
-      }
-    }
-  }
-  float* mine = tile[wave];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int i = (r & 3) + 8 * (r >> 2) + 4 * half;
-    mine[i * DCB_TILE + col] = acc[r];
-  }
-  vec[wave][lane] = sb;
-  __syncthreads();
+  const CbRows rows = {a.x, a.y, a.weight, nullptr, 1};
   const size_t slot = (size_t)arm * a.slices + s;
-  float* out = a.gram + (slot * a.tiles + t) * (DCB_TILE * DCB_TILE);
-  for (int e = threadIdx.x; e < DCB_TILE * DCB_TILE; e += DCB_THREADS)
-    out[e] = ((tile[0][e] + tile[1][e]) + tile[2][e]) + tile[3][e];
-  if (ti == tj && threadIdx.x < DCB_TILE) {
-    float v = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < DCB_WAVES; ++wv) v = (v + vec[wv][threadIdx.x]) + vec[wv][threadIdx.x + 32];
-    a.sb[(slot * a.tiles_1d + ti) * DCB_TILE + threadIdx.x] = v;
-  }
+  cb_gram_tile<DCB_UNROLL, false>(rows, row_begin, row_end, a.d, ti, tj, a.gram + (slot * a.tiles + t) * CB_TILE_ELEMS,
+                                  a.sb + (slot * a.tiles_1d + ti) * CB_TILE, nullptr);
 }
 
-// disjoint_linucb_trainer.py:66-76 on the ordered sums of the partials, per arm (blockIdx.y).  One thread per entry on or
-// above the diagonal (it writes the mirrored entry too: an exactly symmetric matrix whatever was there) and, past those,
-// one per entry of cur_b; thread 0 counts the arm's rows.  cur_A += S and cur_b += S_b are one fp32 add each.
+// disjoint_linucb_trainer.py:66-76 on the ordered sums of the partials, per arm (blockIdx.y): one thread per entry
+// (cb_finish_entry); thread 0 counts the arm's rows.  cur_A += S and cur_b += S_b are one fp32 add each.
 __global__ void dlinucb_finish_kernel(const DcbAccArgs a) {
   const long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int arm = blockIdx.y;
@@ -154,38 +93,30 @@ __global__ void dlinucb_finish_kernel(const DcbAccArgs a) {
     a.cur_num_obs[arm] += (int64_t)(end - begin);
   }
   const size_t slot0 = (size_t)arm * a.slices;
-  if (e < dd) {
-    const int i = (int)(e / a.d), j = (int)(e % a.d);
-    if (i > j) return;
-    const int ti = i / DCB_TILE, tj = j / DCB_TILE;
-    const int t = ti * a.tiles_1d - ti * (ti - 1) / 2 + (tj - ti);
-    const size_t off = (size_t)t * (DCB_TILE * DCB_TILE) + (i % DCB_TILE) * DCB_TILE + (j % DCB_TILE);
-    float S = 0.f;
-    for (int s = 0; s < a.slices; ++s) S += a.gram[(slot0 + s) * a.tiles * (DCB_TILE * DCB_TILE) + off];
-    float* A = a.cur_A + (size_t)arm * dd;
-    const float v = A[e] + S;
-    A[e] = v;
-    A[(long)j * a.d + i] = v;
-  } else {
-    const int i = (int)(e - dd);
-    float S = 0.f;
-    for (int s = 0; s < a.slices; ++s) S += a.sb[(slot0 + s) * a.tiles_1d * DCB_TILE + i];
-    a.cur_b[(size_t)arm * a.d + i] += S;
-  }
+  const CbEntry en = cb_finish_entry(e, a.d, a.tiles_1d, a.tiles, a.slices, a.gram + slot0 * a.tiles * CB_TILE_ELEMS,
+                                     a.sb + slot0 * a.tiles_1d * CB_TILE);
+  if (en.below) return;
+  float* out = en.in_A ? a.cur_A + (size_t)arm * dd : a.cur_b + (size_t)arm * a.d;
+  const float v = out[en.at] + en.S;
+  out[en.at] = v;
+  out[en.mirror] = v;
 }
 
 // ---- scoring ----------------------------------------------------------------------------------------------------------
 // Structure, and why it is not rg_linucb_score's.  That kernel gives a workgroup 32 rows, so every inv_A operand it loads
 // from global memory feeds ONE MFMA, and it waits for each group of loads before the MFMAs that use them.  Here a workgroup
 // takes R row tiles (R = 4: 128 rows, or 2 where x would not fit in LDS), stages ALL d columns of them in LDS once, and
-// reuses that image for every arm and every column tile.  A wave owns output-column tiles jt = wave, wave + 4, ... of
-// Y = X * inv_A[arm] and holds R accumulator tiles: one inv_A operand loaded from global memory feeds R MFMAs, and the loads
-// of the NEXT 16 values of k are issued before the MFMAs of the current ones (registers b_next, a scheduling fence on either
-// side of the MFMA block, the zeroing select after it), so the matrix streams behind the MFMA pipe instead of in front of it.  The X operand comes from LDS as ds_read_b128: within a group of 8 values
-// of k, half h of the wave takes k = 8 g + 4 h + {0..3}, four consecutive floats of its row, and the row pitch is
-// d_pad + 4 floats (d_pad a multiple of 16), which puts 16 consecutive rows on 16 different 16-byte bank slots.  (Which k a
-// half takes in which step is free as long as A and B agree; it only permutes the fp32 summation order, identically in
-// every run.)
+// reuses that image for every arm and every column tile.
+//   - A wave owns output-column tiles jt = wave, wave + 4, ... of Y = X * inv_A[arm] and holds R accumulator tiles: one
+//     inv_A operand loaded from global memory feeds R MFMAs.
+//   - The loads of the NEXT 16 values of k are issued before the MFMAs of the current ones (registers b_next, a scheduling
+//     fence on either side of the MFMA block, the zeroing select after it), so the matrix streams behind the MFMA pipe
+//     instead of in front of it.
+//   - The X operand comes from LDS as ds_read_b128: within a group of 8 values of k, half h of the wave takes
+//     k = 8 g + 4 h + {0..3}, four consecutive floats of its row.  The row pitch is d_pad + 4 floats (d_pad a multiple of
+//     16), which puts 16 consecutive rows on 16 different 16-byte bank slots.  Which k a half takes in which step is free
+//     as long as A and B agree: it only permutes the fp32 summation order, identically in every run.
+// The two scorers share their epilogue's helpers (rg_cb.h: accumulator row, half-wave sum, arg-max rule), not their K loops.
 constexpr int DCB_KG = 2;  // groups of 8 values of k per batch of loads
 
 struct DcbScoreArgs {
@@ -195,19 +126,6 @@ struct DcbScoreArgs {
   int B, d, arms;
   float *mean, *sigma, *ucb;
   int64_t* best_arm;
-};
-
-// the masked arg-max's rule, that of rg_linucb_score: the lowest index among equals, a NaN before any number, arm 0 where
-// no arm is present
-struct DcbBest {
-  float v;
-  int arm;
-  bool found, closed;
-  __device__ __forceinline__ void take(float u, int k, bool present) {
-    if (closed || !present) return;
-    if (!found || u != u || u > v) v = u, arm = k, found = true;
-    if (u != u) closed = true;
-  }
 };
 
 // The inv_A operands of DCB_KG groups of k from k0 on, as loaded (addresses clamped into the matrix whatever k0 is) ...
@@ -231,25 +149,25 @@ __device__ __forceinline__ void dcb_mask_b(int d, int k0, int half, bool j_ok, f
 }
 
 template <int R>
-__global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbScoreArgs a) {
-  constexpr int ROWS = R * DCB_TILE;
+__global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) dlinucb_score_kernel(const DcbScoreArgs a) {
+  constexpr int ROWS = R * CB_TILE;
   RG_DYN_LDS(smem);
   const int d = a.d, arms = a.arms;
   const int dp = (d + 15) & ~15, pitch = dp + 4;
   float* xs = (float*)smem;          // [ROWS][pitch], columns d .. dp - 1 and rows past B zero
-  float* qpart = xs + ROWS * pitch;  // [2][DCB_WAVES][ROWS]
+  float* qpart = xs + ROWS * pitch;  // [2][CB_WAVES][ROWS]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int col = lane & 31, half = lane >> 5;
   const long row0 = (long)blockIdx.x * ROWS;
-  const int tiles_1d = (d + DCB_TILE - 1) / DCB_TILE;
-  for (int r = wave; r < ROWS; r += DCB_WAVES) {
+  const int tiles_1d = cb_tiles_1d(d);
+  for (int r = wave; r < ROWS; r += CB_WAVES) {
     const long row = row0 + r;
     for (int c = lane; c < dp; c += 64) xs[r * pitch + c] = (row < a.B && c < d) ? a.x[row * d + c] : 0.f;
   }
   __syncthreads();
   // the means x . coefs[arm], one (row, arm) pair a thread at a time; they wait in `ucb` for the deviations
   const bool with_sigma = a.alpha != 0.f;
-  for (int p = threadIdx.x; p < ROWS * arms; p += DCB_THREADS) {
+  for (int p = threadIdx.x; p < ROWS * arms; p += CB_THREADS) {
     const int r = p % ROWS, arm = p / ROWS;
     const long row = row0 + r;
     const float* c = a.coefs + (long)arm * d;
@@ -267,8 +185,7 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbS
     }
   }
   __syncthreads();  // (the workgroup's own global stores are visible to it past the barrier)
-  DcbBest best;
-  best.v = 0.f, best.arm = 0, best.found = false, best.closed = false;
+  CbBest best;
   const long my_row = row0 + threadIdx.x;
   const bool finisher = threadIdx.x < ROWS && my_row < a.B;
   if (!with_sigma) {  // the mean alone: inv_A is never read, sigma is exactly 0, ucb has the bits of the mean
@@ -287,8 +204,8 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbS
     for (int rt = 0; rt < R; ++rt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) part[rt][r] = 0.f;
-    for (int jt = wave; jt < tiles_1d; jt += DCB_WAVES) {  // (wave-uniform)
-      const int j = jt * DCB_TILE + col;
+    for (int jt = wave; jt < tiles_1d; jt += CB_WAVES) {  // (wave-uniform)
+      const int j = jt * CB_TILE + col;
       const bool j_ok = j < d;
       const int jc = j_ok ? j : d - 1;
 #pragma unroll
@@ -306,7 +223,7 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbS
           f32x4 av[R];
 #pragma unroll
           for (int rt = 0; rt < R; ++rt)
-            av[rt] = *(const f32x4*)(xs + (rt * DCB_TILE + col) * pitch + k0 + 8 * g + 4 * half);
+            av[rt] = *(const f32x4*)(xs + (rt * CB_TILE + col) * pitch + k0 + 8 * g + 4 * half);
 #pragma unroll
           for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -324,27 +241,22 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbS
       for (int rt = 0; rt < R; ++rt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-          const int i = rt * DCB_TILE + (r & 3) + 8 * (r >> 2) + 4 * half;
+          const int i = rt * CB_TILE + cb_acc_row(r, half);
           const float xv = j_ok ? xs[i * pitch + jc] : 0.f;
           part[rt][r] += acc[rt][r] * xv;
         }
     }
-    float* qp = qpart + (arm & 1) * (DCB_WAVES * ROWS) + wave * ROWS;
+    float* qp = qpart + (arm & 1) * (CB_WAVES * ROWS) + wave * ROWS;
 #pragma unroll
     for (int rt = 0; rt < R; ++rt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        float v = part[rt][r];
-        v += shfl_xor(v, 1);
-        v += shfl_xor(v, 2);
-        v += shfl_xor(v, 4);
-        v += shfl_xor(v, 8);
-        v += shfl_xor(v, 16);
-        if (col == 0) qp[rt * DCB_TILE + (r & 3) + 8 * (r >> 2) + 4 * half] = v;
+        const float v = cb_half_wave_sum(part[rt][r]);
+        if (col == 0) qp[rt * CB_TILE + cb_acc_row(r, half)] = v;
       }
     __syncthreads();  // (one barrier an arm: the next arm writes the other half of qpart)
     if (finisher) {
-      const float* q4 = qpart + (arm & 1) * (DCB_WAVES * ROWS) + threadIdx.x;
+      const float* q4 = qpart + (arm & 1) * (CB_WAVES * ROWS) + threadIdx.x;
       const float q = ((q4[0] + q4[ROWS]) + q4[2 * ROWS]) + q4[3 * ROWS];
       const float sigma = sqrtf(q);  // (a negative form gives NaN, silently: disjoint_linucb_predictor.py:171-173)
       const long o = my_row * arms + arm;
@@ -359,7 +271,7 @@ __global__ void RG_LAUNCH_BOUNDS(DCB_THREADS, 1) dlinucb_score_kernel(const DcbS
 
 static size_t dcb_score_lds_bytes(int rows, int d) {
   const int dp = (d + 15) & ~15;
-  return ((size_t)rows * (dp + 4) + 2 * DCB_WAVES * rows) * sizeof(float);
+  return ((size_t)rows * (dp + 4) + 2 * CB_WAVES * rows) * sizeof(float);
 }
 
 }  // namespace rg
@@ -388,9 +300,9 @@ int rg_dlinucb_accumulate(const float* x, const float* y, const float* weight, c
   a.slice_rows = p.slice_rows;
   a.gram = (float*)workspace, a.sb = a.gram + dcb_gram_floats(p, arms);
   a.cur_A = cur_A, a.cur_b = cur_b, a.cur_num_obs = cur_num_obs;
-  RG_LAUNCH(dlinucb_gram_kernel, dim3(p.slices, p.tiles, arms), dim3(DCB_THREADS), (hipStream_t)stream, a);
+  RG_LAUNCH(dlinucb_gram_kernel, dim3(p.slices, p.tiles, arms), dim3(CB_THREADS), (hipStream_t)stream, a);
   const long entries = (long)dim * dim + dim;
-  RG_LAUNCH(dlinucb_finish_kernel, dim3((unsigned)((entries + DCB_THREADS - 1) / DCB_THREADS), arms), dim3(DCB_THREADS),
+  RG_LAUNCH(dlinucb_finish_kernel, dim3((unsigned)((entries + CB_THREADS - 1) / CB_THREADS), arms), dim3(CB_THREADS),
             (hipStream_t)stream, a);
   return (int)hipGetLastError();
 }
@@ -406,16 +318,16 @@ int rg_dlinucb_score(const float* x, const float* coefs, const float* inv_A, dou
   a.x = x, a.coefs = coefs, a.inv_A = inv_A, a.arm_presence = arm_presence, a.alpha = (float)ucb_alpha;
   a.B = batch, a.d = dim, a.arms = arms, a.mean = mean, a.sigma = sigma, a.ucb = ucb, a.best_arm = best_arm;
   // four row tiles a workgroup where their d columns fit in LDS and the batch has that many rows, two otherwise
-  const bool four = ((dim + 15) & ~15) <= 256 && batch > 2 * DCB_TILE;
-  const int rows = (four ? 4 : 2) * DCB_TILE;
+  const bool four = ((dim + 15) & ~15) <= 256 && batch > 2 * CB_TILE;
+  const int rows = (four ? 4 : 2) * CB_TILE;
   const size_t lds = dcb_score_lds_bytes(rows, dim);
   const dim3 grid((unsigned)((batch + rows - 1) / rows));
   if (four) {
     RG_ALLOW_LDS(dlinucb_score_kernel<4>, lds);
-    RG_LAUNCH_DYN(dlinucb_score_kernel<4>, grid, dim3(DCB_THREADS), lds, (hipStream_t)stream, a);
+    RG_LAUNCH_DYN(dlinucb_score_kernel<4>, grid, dim3(CB_THREADS), lds, (hipStream_t)stream, a);
   } else {
     RG_ALLOW_LDS(dlinucb_score_kernel<2>, lds);
-    RG_LAUNCH_DYN(dlinucb_score_kernel<2>, grid, dim3(DCB_THREADS), lds, (hipStream_t)stream, a);
+    RG_LAUNCH_DYN(dlinucb_score_kernel<2>, grid, dim3(CB_THREADS), lds, (hipStream_t)stream, a);
   }
   return (int)hipGetLastError();
 }

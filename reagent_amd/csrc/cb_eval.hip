@@ -4,7 +4,8 @@
 // add_importance_weights (evaluation/cb/utils.py:9-47), _process_used_data (policy_evaluator.py:38-68) — and the
 // trainer's sum_weight_since_update_local += ... (reagent/training/cb/base_trainer.py:127-129) in one main and one
 // finishing launch on device-resident state.  No atomics, no host synchronisation: per-workgroup partials (double) leave
-// the main launch and the finishing launch adds them in a fixed order, so two runs give the same bits.
+// the main launch and the finishing launch adds them in a fixed order, so two runs give the same bits.  The fp64 wave sum
+// and the LDS tree of the finishing launch are rg_reduce.h's, shared with the other bandit files (see rg_cb.h).
 //
 // A QUIRK OF THE REFERENCE THAT IS KEPT.  Without arm_presence the reference's `sizes` is [B, 1] while `weights.squeeze()`
 // is [B]: their product broadcasts to [B, B], and the two size sums come out `batch` times too large (B * A * sum w;
@@ -12,6 +13,7 @@
 // finishing launch multiplies the two size sums by `batch` where arm_presence is NULL.  With arm_presence they are plain.
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
+#include "rg_reduce.h"  // wave_sum_f64, lds_tree_sum
 
 // every row value is held to the reference's fp32 operation order: each multiply and divide is rounded on its own
 #pragma clang fp contract(off)
@@ -33,16 +35,6 @@ struct CbEvalArgs {
   double* partials;  // [CBE_SUMS][P]
   int P;
 };
-
-__device__ __forceinline__ double cbe_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) {
-    const long long b = __builtin_bit_cast(long long, v);
-    const int lo = shfl_xor((int)b, off), hi = shfl_xor((int)(b >> 32), off);
-    v += __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-  }
-  return v;
-}
 
 // Thread t of workgroup g has row r = 256 g + t.  Adjacent lanes read adjacent rows, so every load of a wave covers one
 // contiguous span (512 bytes of action, 256 of reward, 64 * arms of arm_presence) and every fetched line is used whole.
@@ -83,7 +75,7 @@ __global__ void RG_LAUNCH_BOUNDS(CBE_THREADS, 1) cb_eval_ingest_kernel(const CbE
     t[7] = (double)(wacc * fsize);
   }
 #pragma unroll
-  for (int k = 0; k < CBE_SUMS; ++k) t[k] = cbe_wave_sum_f64(t[k]);
+  for (int k = 0; k < CBE_SUMS; ++k) t[k] = wave_sum_f64(t[k]);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int k = 0; k < CBE_SUMS; ++k) wave_sums[threadIdx.x >> 6][k] = t[k];
@@ -110,11 +102,7 @@ __global__ void RG_LAUNCH_BOUNDS(CBE_THREADS, 1) cb_eval_finish_kernel(const dou
   double v = 0.0;
   for (int p = j; p < P; p += CBE_FINISH_LANES) v += partials[(long)k * P + p];
   sums[threadIdx.x] = v;
-  __syncthreads();
-  for (int off = CBE_FINISH_LANES / 2; off >= 1; off >>= 1) {
-    if (j < off) sums[threadIdx.x] += sums[threadIdx.x + off];
-    __syncthreads();
-  }
+  lds_tree_sum<CBE_FINISH_LANES>(sums);
   if (j == 0) {
     double total = sums[threadIdx.x];
     if (k == 2 || k == 7) total *= size_scale;

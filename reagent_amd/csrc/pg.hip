@@ -5,6 +5,7 @@
 // leave as per-workgroup partials in a fixed order (rg_reduce_sum finishes them).
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
+#include "rg_reduce.h"  // shfl_xor_f64, wave_sum_f64
 
 // The scan is held to the reference's bits: a multiply and an add, each rounded.  hipcc contracts a * b + c into a fused
 // multiply-add by default, and the runtime's __fmul_rn / __fadd_rn are plain operators compiled under that default: inlined,
@@ -22,21 +23,6 @@ __device__ __forceinline__ float pg_div(float a, float b) { return a / b; }
 constexpr int PG_THREADS = 256;
 constexpr int PG_WAVES = PG_THREADS / 64;
 constexpr float PG_INVALID_ACTION = -1e10f;  // INVALID_ACTION_CONSTANT (models/dqn.py:13)
-
-__device__ __forceinline__ double pg_shfl_xor_f64(double v, int off) {
-  long long b;
-  memcpy(&b, &v, 8);
-  const int lo = shfl_xor((int)b, off), hi = shfl_xor((int)(b >> 32), off);
-  b = ((long long)hi << 32) | (long long)(unsigned)lo;
-  memcpy(&v, &b, 8);
-  return v;
-}
-
-__device__ __forceinline__ double pg_wave_sum_f64(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += pg_shfl_xor_f64(v, off);
-  return v;
-}
 
 // discounted_returns (training/utils.py:42-54) on clamp(reward, max = clip) (reinforce_trainer.py:106-108), then whiten
 // (utils.py:32-39) or REINFORCE's mean subtraction (:113-114), then clamp(min = 0) (:115-116).  One wave per trajectory
@@ -83,7 +69,7 @@ __global__ void pg_returns_kernel(const float* __restrict__ reward, const int32_
     const long i = e - 1 - ((long)c << 6) - lane;
     if (i >= s) sum += (double)out[i];
   }
-  const double mean = len > 0 ? pg_wave_sum_f64(sum) / (double)len : 0.0;
+  const double mean = len > 0 ? wave_sum_f64(sum) / (double)len : 0.0;
   float denom = 1.f;
   if (normalize) {  // x.std(unbiased=False) + EPS, EPS = float64's epsilon added in fp32
     double ss = 0.0;
@@ -94,7 +80,7 @@ __global__ void pg_returns_kernel(const float* __restrict__ reward, const int32_
         ss += d * d;
       }
     }
-    const double var = len > 0 ? pg_wave_sum_f64(ss) / (double)len : 0.0;
+    const double var = len > 0 ? wave_sum_f64(ss) / (double)len : 0.0;
     denom = pg_add((float)sqrt(var), 2.220446049250313e-16f);
   }
   const float mean_f = subtract_mean ? (float)mean : 0.f;
@@ -113,18 +99,18 @@ __global__ void pg_returns_kernel(const float* __restrict__ reward, const int32_
 template <int G>
 __device__ __forceinline__ double pg_group_max(double v) {
 #pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v = fmax(v, pg_shfl_xor_f64(v, off));
+  for (int off = G / 2; off >= 1; off >>= 1) v = fmax(v, shfl_xor_f64(v, off));
   return v;
 }
 template <int G>
 __device__ __forceinline__ double pg_group_sum(double v) {
 #pragma unroll
-  for (int off = G / 2; off >= 1; off >>= 1) v += pg_shfl_xor_f64(v, off);
+  for (int off = G / 2; off >= 1; off >>= 1) v += shfl_xor_f64(v, off);
   return v;
 }
 
 __device__ __forceinline__ double pg_block_sum(double v, double* scratch) {
-  v = pg_wave_sum_f64(v);
+  v = wave_sum_f64(v);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
   __syncthreads();
   const double s = (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);

@@ -1,5 +1,6 @@
 // rg_reduce.h — workgroup reductions shared by the loss heads (heads.hip, crr.hip) and by the fused stack's backward and
-// weight-gradient launches (mlp_fused.hip, mlp_wgrad.hip: the bias gradients' column reduce and its argument table).
+// weight-gradient launches (mlp_fused.hip, mlp_wgrad.hip: the bias gradients' column reduce and its argument table), and the
+// fp64 wave sum and the 256-value LDS tree of the bandit, policy-gradient and SAC files.
 #pragma once
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
@@ -17,6 +18,31 @@ __device__ __forceinline__ float block_sum_256(float v, float* scratch /*[4]*/) 
   const float s = (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);
   __syncthreads();
   return s;
+}
+
+// lane ^ off's double, moved as its two words; the sum of a double over the 64 lanes of a wave by butterflies (offsets 32
+// down to 1), the same bits in every lane
+__device__ __forceinline__ double shfl_xor_f64(double v, int off) {
+  const long long b = __builtin_bit_cast(long long, v);
+  const int lo = shfl_xor((int)b, off), hi = shfl_xor((int)(b >> 32), off);
+  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
+}
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v += shfl_xor_f64(v, off);
+  return v;
+}
+
+// A 256-thread workgroup's values vals[threadIdx.x], already written, summed in place by a fixed tree inside every segment
+// of SEG consecutive threads: the segment's sum ends in its first slot (visible to all threads on return).
+template <int SEG, typename T>
+__device__ __forceinline__ void lds_tree_sum(T* vals) {
+  const int j = threadIdx.x % SEG;
+  __syncthreads();
+  for (int off = SEG / 2; off >= 1; off >>= 1) {
+    if (j < off) vals[threadIdx.x] += vals[threadIdx.x + off];
+    __syncthreads();
+  }
 }
 
 // this thread's share in[tid], in[tid + 256], ... of a sum over n values, as 16 independent partial sums combined in a fixed

@@ -4,6 +4,7 @@
 #include <rg_platform.h>
 #include "rg_optim.h"
 #include "../../include/reagent_hip.h"
+#include "rg_reduce.h"  // wave_sum_f64
 
 namespace rg {
 
@@ -408,12 +409,7 @@ int rg_gaussian_head_backward(const float* loc_scale, int64_t ldls, const float*
 // fixed order; the per-dimension terms are summed by one thread of the finishing launch.
 constexpr int KLD_THREADS = 256;
 __device__ __forceinline__ double block_sum_f64(double v, double* scratch) {
-  // wave reduction through shuffles of the two halves
-  for (int off = 32; off >= 1; off >>= 1) {
-    const long long bits = __builtin_bit_cast(long long, v);
-    const int lo = shfl_xor((int)bits, off), hi = shfl_xor((int)(bits >> 32), off);
-    v += __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned)lo);
-  }
+  v = wave_sum_f64(v);
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
   __syncthreads();
   const double s = (scratch[0] + scratch[1]) + (scratch[2] + scratch[3]);

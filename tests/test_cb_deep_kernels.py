@@ -18,15 +18,13 @@ Head.  The float64 statement under autograd; fp32 bounds for ANY summation order
     dv[c]: sum_r e_dlin |z_rc| + (B + 2) u sum_r |dlin_r z_rc|
 """
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 import torch.nn.functional as Fn
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from kernel_remarks import HIPCC, kernel_resources
+
 U = 2.0 ** -24
 F32, F64 = torch.float32, torch.float64
 EINVAL = -1
@@ -338,21 +336,7 @@ def test_bad_arguments_are_refused(backend):
 def test_cb_deep_kernels_have_no_scratch(tmp_path):
     """cb_deep.hip compiled for gfx950 with the resource remarks on: no scratch, no spilled register (the solve keeps its
     8 x 8 share of the matrix in registers under compile-time indices), and the LDS the header states"""
-    csrc = os.path.join(ROOT, "reagent_amd", "csrc")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{csrc}", f"-I{ROOT}/include",
-                          "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "cb_deep.hip"),
-                          "-o", str(tmp_path / "o.o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "VGPRs"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                kernels[name].setdefault(key, int(m.group(1)))
+    kernels = kernel_resources("cb_deep.hip", tmp_path)
     for want, n in (("linucb_solve_kernel", 4), ("drlinucb_head_kernel", 4), ("drlinucb_finish_kernel", 1),
                     ("drlinucb_activate_kernel", 1)):
         assert sum(want in k for k in kernels) == n, (want, list(kernels))

@@ -8,14 +8,12 @@ The bounds are those of fp32 arithmetic in ANY summation order, per arm and entr
     |sigma^2 - q64| <= (2 d + 8) u sum_ij |x_i M_ij x_j|
 torch's own fp32 `x.t() @ (x * w)` is held to the first term in the same test, so the bound is fair to the reference."""
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from kernel_remarks import HIPCC, kernel_resources
+
 U = 2.0 ** -24
 F32, F64 = torch.float32, torch.float64
 SIZES = [0, 1, 63, 64, 65, 257]
@@ -328,22 +326,7 @@ def test_bad_arguments_are_refused(backend):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_cb_disjoint_kernels_have_no_scratch(tmp_path):
     """cb_disjoint.hip compiled for gfx950 with the resource remarks on: its kernels, no scratch, no spilled register"""
-    csrc = os.path.join(ROOT, "reagent_amd", "csrc")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{csrc}", f"-I{ROOT}/include",
-                          "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c",
-                          os.path.join(csrc, "cb_disjoint.hip"), "-o", str(tmp_path / "o.o")],
-                         capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                kernels[name].setdefault(key, int(m.group(1)))
+    kernels = kernel_resources("cb_disjoint.hip", tmp_path)
     for want, count in (("dlinucb_gram_kernel", 1), ("dlinucb_finish_kernel", 1), ("dlinucb_score_kernel", 2)):
         assert sum(want in k for k in kernels) == count, (want, list(kernels))
     assert len(kernels) == 4

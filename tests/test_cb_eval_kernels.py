@@ -25,14 +25,12 @@ their own bound above.  Without exp the two sets of importance weights are the s
 """
 import itertools
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from kernel_remarks import HIPCC, kernel_resources
+
 U = 2.0 ** -24
 EINVAL = -1
 F32, F64 = torch.float32, torch.float64
@@ -301,21 +299,7 @@ def test_einval(backend):
 def test_cb_eval_kernels_have_no_scratch(tmp_path):
     """cb_eval.hip compiled for gfx950 with the resource remarks on: no scratch, no spilled register, and the LDS the two
     kernels declare (4 waves x 8 doubles; 256 doubles)"""
-    csrc = os.path.join(ROOT, "reagent_amd", "csrc")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{csrc}", f"-I{ROOT}/include",
-                          "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "cb_eval.hip"),
-                          "-o", str(tmp_path / "o.o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]", "VGPRs"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                kernels[name].setdefault(key, int(m.group(1)))
+    kernels = kernel_resources("cb_eval.hip", tmp_path)
     for want, lds in (("cb_eval_ingest_kernel", 4 * 8 * 8), ("cb_eval_finish_kernel", 256 * 8)):
         (k,) = [k for k in kernels if want in k]
         v = kernels[k]

@@ -9,14 +9,12 @@ The bounds are those of fp32 arithmetic in ANY summation order, per entry:
     |sigma^2 W - q64| <= (2 d + 8) u sum_ij |x_i M_ij x_j|
 torch's own fp32 `x.t() @ (x * w)` is held to the first one in the same test, so the bound is fair to the reference."""
 import os
-import re
-import subprocess
 
 import pytest
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = "/opt/rocm/bin/hipcc"
+from kernel_remarks import HIPCC, kernel_resources
+
 U = 2.0 ** -24
 F32, F64 = torch.float32, torch.float64
 
@@ -115,6 +113,30 @@ def test_accumulate_d512_on_the_device():
     _accumulate(state, x, y, w)
     _check_update(state, want, abs_sums, B, (B, d))
     assert torch.equal(state[0], state[0].t()) and state[3].item() == B
+
+
+@pytest.mark.parametrize("weighted", [False, True])
+@pytest.mark.parametrize("d", [3, 33, 130])
+@pytest.mark.parametrize("B", [1, 65, 256])
+def test_the_joint_and_disjoint_accumulate_paths_are_one_arithmetic(backend, B, d, weighted):
+    """From a state of exact zeros (cur_sum_weight included) the running average of one batch is S / s_w, and the disjoint
+    kernels' one arm over the same rows holds S itself: cur_avg_A == cur_A[0] / cur_sum_weight and cur_avg_b == cur_b[0] /
+    cur_sum_weight bit for bit (one fp32 division each), both counters B.  This holds the two Gram kernels to one walk over
+    the rows, one merge of the waves and one order over the slices.  B stays at or below 256: above it the two plans cut
+    the rows into different slices (cb_plan by (B, d), dcb_plan by d alone) and the bits legitimately differ."""
+    from reagent_amd import ops
+
+    dev = backend.device
+    x, y, w = _batch(B, d, weighted, 31 * B + d, dev)
+    joint = _fresh(d, dev, 0.0)
+    _accumulate(joint, x, y, w)
+    cur_A, cur_b = torch.zeros(1, d, d, device=dev), torch.zeros(1, d, device=dev)
+    obs = torch.zeros(1, dtype=torch.int64, device=dev)
+    offsets = torch.tensor([0, B], dtype=torch.int64).to(dev)
+    ops.dlinucb_accumulate(x, y, w, offsets, B, cur_A, cur_b, obs, ops.dlinucb_workspace(B, 1, d, dev))
+    assert joint[2].item() > 0
+    assert torch.equal(joint[0], cur_A[0] / joint[2]) and torch.equal(joint[1], cur_b[0] / joint[2])
+    assert joint[3].item() == B and obs.item() == B
 
 
 @pytest.mark.parametrize("A", [1, 5])
@@ -276,21 +298,7 @@ def test_negative_definite_matrix_counts_every_row_and_forward_raises(backend):
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 def test_cb_kernels_have_no_scratch(tmp_path):
     """cb.hip compiled for gfx950 with the resource remarks on: its four kernels, no scratch, no spilled register"""
-    csrc = os.path.join(ROOT, "reagent_amd", "csrc")
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{csrc}", f"-I{ROOT}/include",
-                          "-Wno-unused-result", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(csrc, "cb.hip"),
-                          "-o", str(tmp_path / "o.o")], capture_output=True, text=True, timeout=900)
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, name = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            kernels[name] = {}
-        for key in ("VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]"):
-            m = re.search(re.escape(key) + r": (\d+)", line)
-            if m and name:
-                kernels[name].setdefault(key, int(m.group(1)))
+    kernels = kernel_resources("cb.hip", tmp_path)
     for want in ("linucb_gram_kernel", "linucb_finish_kernel", "linucb_score_kernel", "linucb_select_kernel"):
         assert sum(want in k for k in kernels) == 1, (want, list(kernels))
     assert len(kernels) == 4
