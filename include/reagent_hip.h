@@ -715,7 +715,8 @@ int rg_pg_head(const float* scores, int64_t ld_scores, const float* possible_act
  * [rg_linucb_score_partials(n)] int32: rows with a NaN sigma per workgroup.  A finishing launch adds them in order into
  * nan_count [1] (plain stores, no atomics) and, for arms > 0, writes best_arm [n / arms] int64 = the arg-max of ucb over
  * each row's arms under arm_presence ([n] bytes, nonzero = present; NULL = all), the lowest index among equals
- * (get_model_actions, reagent/training/cb/utils.py:113-139, randomize_ties = False); arm 0 for a row with no arm present.
+ * (get_model_actions, reagent/training/cb/utils.py:113-139, randomize_ties = False), the first present NaN before any
+ * number; arm 0 for a row with no arm present or with every present arm at -inf (a present -inf counts as an absent arm).
  * RG_EINVAL for n < 1, dim < 1, dim > RG_LINUCB_MAX_DIM, arms < 0, n not a multiple of arms, a null pointer. */
 #define RG_LINUCB_MAX_DIM 512
 size_t rg_linucb_workspace_bytes(int batch, int dim);
@@ -753,8 +754,9 @@ int rg_linucb_score(const float* x, const float* coefs, const float* inv_avg_A, 
  * is exactly 0 and ucb has the bits of mean.  ucb [batch, arms] is required; mean and sigma [batch, arms] may be NULL.
  * best_arm [batch] int64 (or NULL), from the same launch: the arg-max of ucb over the arms arm_presence ([batch, arms] bytes,
  * nonzero = present; NULL = all) marks present, the lowest index among equals, a NaN before any number (rg_linucb_score's
- * rule), arm 0 for a row with no arm present (get_model_actions, reagent/training/cb/utils.py:113-139).  A workgroup stages
- * its rows of x in LDS once and reuses them for every arm; x * inv_A[a] stays in MFMA accumulators.  One launch.
+ * rule), arm 0 for a row with no arm present or with every present arm at -inf (get_model_actions,
+ * reagent/training/cb/utils.py:113-139).  A workgroup stages its rows of x in LDS once and reuses them for every arm;
+ * x * inv_A[a] stays in MFMA accumulators.  One launch.
  * RG_EINVAL for batch < 1, arms < 1, dim < 1, dim > RG_LINUCB_MAX_DIM, batch * arms >= 2^31, a null x / coefs / inv_A / ucb,
  * arm_presence without best_arm. */
 size_t rg_dlinucb_workspace_bytes(int max_arm_rows, int arms, int dim);

@@ -213,8 +213,9 @@ __global__ void RG_LAUNCH_BOUNDS(CB_THREADS, 1) drlinucb_head_kernel(const DrHea
     } else if (a.loss == RG_CB_LOSS_MAE) {
       lr = fabsf(diff);
       gr = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-    } else {  // F.binary_cross_entropy: both logs clamped at -100; its backward's denominator at 1e-12
-      const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(logf(1.f - p), -100.f);
+    } else {  // F.binary_cross_entropy: both logs clamped at -100 (log1p(-p), as torch takes it: 1 - p is 1 below
+              // p = 2^-24 and the row's loss would vanish); its backward's denominator at 1e-12
+      const float lp = fmaxf(logf(p), -100.f), l1p = fmaxf(log1pf(-p), -100.f);
       lr = (y - 1.f) * l1p - y * lp;
       gr = diff / fmaxf((1.f - p) * p, 1e-12f);
     }

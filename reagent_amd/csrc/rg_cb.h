@@ -40,14 +40,18 @@ __device__ __forceinline__ float cb_half_wave_sum(float v) {
   return v;
 }
 
-// The masked arg-max's rule (torch.argmax under arm_presence): the lowest index among equals, a NaN before any number, arm
-// 0 where no arm is present.  take() is called with the arms in rising order; past a NaN nothing changes (closed).
+// The masked arg-max's rule: torch.argmax of the scores with every absent arm's score replaced by -inf, which is what the
+// reference's masked argmax computes (tests/golden/cb/argmax_nonfinite.npz holds its answers).  The lowest index among
+// equals, the first present NaN before any number, and arm 0 where nothing beats -inf (no arm present, or every present
+// arm at -inf): a present -inf is worth what an absent arm is, and is passed over like one.  take() is called with the arms
+// in rising order; past a NaN nothing changes (closed).  (Written as a skip, not as a start from v = -inf: that form, one
+// register shorter, made hipcc spill two VGPRs in dlinucb_score_kernel<4>, which sits at 256.)
 struct CbBest {
   float v = 0.f;
   int arm = 0;
   bool found = false, closed = false;
   __device__ __forceinline__ void take(float u, int k, bool present) {
-    if (closed || !present) return;
+    if (closed || !present || u == -INFINITY) return;
     if (!found || u != u || u > v) v = u, arm = k, found = true;
     if (u != u) closed = true;
   }

@@ -32,8 +32,10 @@ def add_chosen_arm_features(batch: Union[CBInput, List[CBInput]]) -> CBInput:
 
 def get_model_actions(scores: torch.Tensor, mask: Optional[torch.Tensor] = None, randomize_ties: bool = False) -> torch.Tensor:
     """[B, 1] int64: each row's arg-max of scores [B, arms] over the arms `mask` marks present, the lowest index among
-    equals (utils.py:113-139 with randomize_ties = False).  It is rg_linucb_score's arg-max: the scores pass as a
-    one-feature model with coefficient 1 and ucb_alpha 0, whose ucb is the score itself, bit for bit."""
+    equals (utils.py:113-139 with randomize_ties = False).  Non-finite scores follow the reference too: the first present
+    NaN wins; an absent arm counts as -inf, so a row with no arm present, or whose present arms are all -inf, gives arm 0.
+    It is rg_linucb_score's arg-max: the scores pass as a one-feature model with coefficient 1 and ucb_alpha 0, whose ucb
+    is the score itself, bit for bit."""
     if randomize_ties:
         raise NotImplementedError("get_model_actions(randomize_ties=True) (argmax_random_tie_breaks) is not implemented")
     assert scores.ndim == 2

@@ -197,18 +197,17 @@ def _score_inputs(B, d, arms, dev, seed=0):
     return x.to(dev), c.to(dev), M.to(dev)
 
 
-@pytest.mark.parametrize("alpha", [0.0, 1.5])
-@pytest.mark.parametrize("arms", [1, 5])
-@pytest.mark.parametrize("d", [1, 33, 130])
-@pytest.mark.parametrize("B", [1, 33, 65])
-def test_score_against_float64(backend, B, d, arms, alpha):
-    x, c, M = _score_inputs(B, d, arms, backend.device)
+def _check_score_against_float64(dev, B, d, arms, alpha):
+    """the module's score bounds at one shape; prints the worst error / bound of the mean and of sigma^2"""
+    x, c, M = _score_inputs(B, d, arms, dev)
     if alpha == 0.0:
         M = torch.full_like(M, float("nan"))  # never read
     out, _ = _score(x, c, M, alpha)
     x64, c64, M64 = x.cpu().double(), c.cpu().double(), M.cpu().double()
     mean, sigma, ucb = (t.cpu() for t in out)
-    assert ((mean.double() - x64 @ c64.t()).abs() <= (d + 2) * U * (x64.abs() @ c64.abs().t())).all()
+    mean_err, mean_bound = (mean.double() - x64 @ c64.t()).abs(), (d + 2) * U * (x64.abs() @ c64.abs().t())
+    ratios = [(mean_err / mean_bound.clamp_min(1e-300)).max().item(), 0.0]
+    assert (mean_err <= mean_bound).all()
     if alpha == 0.0:
         assert torch.isfinite(out).all()
         assert torch.equal(sigma, torch.zeros(B, arms)) and torch.equal(ucb.view(torch.int32), mean.view(torch.int32))
@@ -216,6 +215,7 @@ def test_score_against_float64(backend, B, d, arms, alpha):
         q64 = torch.einsum("ijk,jk->ji", torch.matmul(x64, M64), x64)
         qabs = torch.einsum("ijk,jk->ji", torch.matmul(x64.abs(), M64.abs()), x64.abs())
         err = (sigma.double() ** 2 - q64).abs()
+        ratios[1] = (err / ((2 * d + 8) * U * qabs)).max().item()
         assert (err <= (2 * d + 8) * U * qabs).all(), (err / qabs).max().item() / U
         assert torch.equal(ucb, mean + torch.tensor(alpha) * sigma)  # one multiply and one add in fp32
     again, _ = _score(x, c, M, alpha)
@@ -226,6 +226,122 @@ def test_score_against_float64(backend, B, d, arms, alpha):
     alone = torch.empty(B, arms, device=x.device)
     ops.dlinucb_score(x, c, M, alpha, alone)
     assert torch.equal(alone, out[2])
+    print(f"dlinucb_score B={B} d={d} arms={arms} alpha={alpha}: mean {ratios[0]:.4f} of its bound, sigma^2 {ratios[1]:.4f}")
+
+
+@pytest.mark.parametrize("alpha", [0.0, 1.5])
+@pytest.mark.parametrize("arms", [1, 5])
+@pytest.mark.parametrize("d", [1, 33, 130])
+@pytest.mark.parametrize("B", [1, 33, 65])
+def test_score_against_float64(backend, B, d, arms, alpha):
+    _check_score_against_float64(backend.device, B, d, arms, alpha)
+
+
+@pytest.mark.parametrize("d", [256, 257, 385, 512])
+@pytest.mark.parametrize("B", [33, 65])
+def test_score_over_the_whole_legal_width(backend, B, d):
+    """the widths the two-row-tile kernel exists for (d > 256: four tiles of x do not fit in LDS) and the largest dynamic
+    LDS requests: R = 4 at (B, d) = (65, 256), about 137 KB, R = 2 everywhere else, about 134 KB at d = 512.  Two arms with
+    different matrices; B = 33 and 65 leave one live row in the last row tile.  The bounds are
+    test_score_against_float64's."""
+    _check_score_against_float64(backend.device, B, d, 2, 1.5)
+
+
+@pytest.mark.parametrize("d", [33, 200, 257, 512])
+def test_score_of_integer_inputs_is_exact(backend, d):
+    """Small integer inputs (x, coefs in [-3, 3]; M = G + G^T + round(8 sqrt(d)) I, G in [-2, 2]; another M and coefs per
+    arm): every product and every partial sum, in any order, is an integer below 2^24, so the mean is bit-equal to x @ c and
+    round(sigma^2) == q exactly.  One dropped, doubled or misplaced (i, j) term fails at any d, where the any-order bound
+    (which grows with d) would let it pass.  q < 2^20: a sigma 2 ulp off moves sigma^2 by less than q 2^-21 < 1/2."""
+    dev, N, arms = backend.device, 40, 2
+    g = torch.Generator().manual_seed(29 + d)
+    x = torch.randint(-3, 4, (N, d), generator=g).float()
+    c = torch.randint(-3, 4, (arms, d), generator=g).float()
+    G = torch.randint(-2, 3, (arms, d, d), generator=g).float()
+    M = (G + G.transpose(1, 2) + round(8 * d ** 0.5) * torch.eye(d)).contiguous()
+    x64, M64 = x.double(), M.double()
+    q64 = torch.einsum("ijk,jk->ji", torch.matmul(x64, M64), x64)
+    qabs = torch.einsum("ijk,jk->ji", torch.matmul(x64.abs(), M64.abs()), x64.abs())
+    assert qabs.max().item() < 2.0 ** 24 and (x64.abs() @ c.double().abs().t()).max().item() < 2.0 ** 24  # the sums are exact
+    assert q64.min().item() > 0 and q64.max().item() < 2.0 ** 20
+    out, _ = _score(x.to(dev), c.to(dev), M.to(dev), 1.5)
+    mean, sigma, ucb = (t.cpu() for t in out)
+    assert torch.equal(mean.double(), x64 @ c.double().t())
+    got_q = torch.round(sigma.double() ** 2)
+    assert torch.equal(got_q, q64), (got_q - q64).abs().max().item()
+    assert torch.equal(ucb, mean + torch.tensor(1.5) * sigma)
+    ulps = (sigma.view(torch.int32).long() - q64.sqrt().float().view(torch.int32).long()).abs().max().item()
+    print(f"dlinucb_score exact d={d}: max qabs {qabs.max().item():.3e}, q in [{q64.min().item():.0f}, "
+          f"{q64.max().item():.0f}], sigma within {ulps} ulp of sqrt(q)")
+
+
+@pytest.mark.parametrize("B,d", [(65, 33), (300, 257), (600, 33)])
+def test_accumulate_of_integer_inputs_is_exact(backend, B, d):
+    """x, y integers in [-3, 3], w in {1, 2, 4}: every partial sum is an integer far below 2^24, so from a zero state
+    cur_A[a] == S and cur_b[a] == S_b EXACTLY, per arm (one of B rows, one of 5; (600, 33) is three slices)"""
+    dev = backend.device
+    g = torch.Generator().manual_seed(5 * B + d)
+    subs = []
+    for n in (B, 5):
+        x, y = torch.randint(-3, 4, (n, d), generator=g).float(), torch.randint(-3, 4, (n,), generator=g).float()
+        subs.append((x, y, torch.tensor([1.0, 2.0, 4.0])[torch.randint(0, 3, (n,), generator=g)]))
+    state = _fresh(2, d, dev)
+    _accumulate(state, subs, dev)
+    for a, sub in enumerate(subs):
+        (S, Sb), _ = _sums(sub)
+        assert torch.equal(state[0][a].cpu().double(), S) and torch.equal(state[1][a].cpu().double(), Sb), a
+        assert S.abs().max().item() > 0 and state[2][a].item() == sub[0].shape[0]
+
+
+def test_accumulate_with_slices_longer_than_one_unit(backend):
+    """d = 130: 15 tiles, so dcb_plan cuts an arm into slices of 3 x 256 = 768 rows; arms of 800, 0 and 769 rows take two
+    slices each (the second of 32 rows and of one).  The module's bound per arm, and the arm of 800 rows in a call of its
+    own gives the same bits."""
+    dev, d = backend.device, 130
+    subs = _subs([800, 0, 769], d, True, 41)
+    state = _fresh(3, d, dev)
+    before = [t.clone() for t in state]
+    _accumulate(state, subs, dev)
+    _check(state, before, subs, "long slices")
+    for a, sub in enumerate(subs):
+        if sub[0].shape[0]:
+            (S, _), (absS, _) = _sums(sub)
+            n = sub[0].shape[0]
+            ratio = ((state[0][a].cpu().double() - S).abs() / ((n + 2) * U * absS + 2 * U * S.abs())).max().item()
+            print(f"dlinucb_accumulate d={d} arm of {n} rows: cur_A {ratio:.4f} of its bound")
+    assert not state[0][1].any() and not state[1][1].any() and state[2].tolist() == [800, 0, 769]
+    alone = _fresh(1, d, dev)
+    _accumulate(alone, subs[:1], dev)
+    assert torch.equal(alone[0][0], state[0][0]) and torch.equal(alone[1][0], state[1][0])
+
+
+@pytest.mark.parametrize("arms", [3, 5])
+def test_best_arm_on_non_finite_scores_is_the_references(backend, arms):
+    """tests/golden/cb/argmax_nonfinite.npz: the unmodified reference's get_model_actions on rows with NaN and +-inf among
+    present and absent arms.  At d = 1, x = 1 and ucb_alpha = 0 the ucb of arm a is coefs[a] itself, so a row of the
+    fixture is planted through coefs; every row with the same scores goes into one call, one batch row per mask.  The
+    first present NaN wins, a present -inf is worth what an absent arm is, arm 0 where nothing beats -inf."""
+    import numpy as np
+
+    from golden_util import GOLDEN
+
+    dev = backend.device
+    with np.load(os.path.join(GOLDEN, "cb", "argmax_nonfinite.npz")) as z:
+        scores, mask, masked, plain = (torch.from_numpy(z[f"a{arms}_{k}"])
+                                       for k in ("scores", "mask", "actions_masked", "actions_plain"))
+    groups = {}
+    for r in range(scores.shape[0]):
+        groups.setdefault(tuple(scores[r].view(torch.int32).tolist()), []).append(r)
+    assert len(groups) >= 4
+    for rows in groups.values():
+        B = len(rows)
+        c = scores[rows[0]].view(arms, 1).to(dev)
+        out, best = _score(torch.ones(B, 1, device=dev), c, torch.ones(arms, 1, 1, device=dev), 0.0,
+                           presence=mask[rows].to(dev))
+        assert torch.equal(out[2].cpu().view(torch.int32), scores[rows].view(torch.int32))  # the scores, bit for bit
+        assert torch.equal(best.cpu(), masked[rows].reshape(-1)), (scores[rows[0]], mask[rows], best)
+        _, best = _score(torch.ones(1, 1, device=dev), c, torch.ones(arms, 1, 1, device=dev), 0.0, want_best=True)
+        assert best.item() == plain[rows[0]].item(), scores[rows[0]]
 
 
 def test_a_negative_definite_arm_is_nan_in_its_own_column_only(backend):
