@@ -845,6 +845,30 @@ int rg_cb_eval_ingest(const int64_t* action, const int64_t* model_action, const 
                       float* sum_importance_weight_accepted, float* sum_size_weighted_accepted,
                       float* sum_weight_since_update, rg_stream_t stream);
 
+/* ABI 20 — rg_linucb_solve_blocked: rg_linucb_solve's contract, word for word, for 1 <= dim <= RG_LINUCB_MAX_DIM (the
+ * deep-represent model's solve where its last layer is 128 to 511 wide).  Fold (reduce_avg) in the reference's fp32
+ * operation order, bit for bit, an elementwise launch; A_ext = avg_A + (float(l2_reg_lambda) * 1) / sum_weight on the
+ * diagonal; inv_avg_A = A_ext^-1; coefs = inv_avg_A * avg_b; coefs_valid_for_avg_A = avg_A; cur_avg_A, cur_avg_b,
+ * cur_sum_weight and cur_num_obs leave exactly zero; inv_avg_A leaves EXACTLY symmetric (the tiles on or above the
+ * diagonal are computed and mirrored).  The route is a blocked Cholesky factorisation in 32 x 32 blocks, n = ceil(dim / 32),
+ * on three P x P fp32 matrices (P = 32 n) in `workspace` (rg_linucb_solve_blocked_workspace_bytes(dim) = 12 P^2 bytes; 0
+ * for a dim the call refuses): A_ext padded with the identity, L^T with A_ext = L L^T (only the lower triangle of A_ext is
+ * read) and W = L^-1.  n + 3 launches, ordered by the stream alone (no cooperative launch, no flag a workgroup waits on):
+ * the fold; one launch per block column k in which every workgroup factors the diagonal block S_kk = A_kk - sum_{j<k}
+ * L_kj L_kj^T for itself (unblocked, in LDS) and inverts the factor by substitution (W_kk), then one workgroup each forms
+ * a panel block L_gk = (A_gk - sum_{j<k} L_gj L_kj^T) W_kk^T (g > k) or a block of row k of the block substitution
+ * W_kg = -W_kk sum_{g<=j<k} L_kj W_jg (g < k); inv = W^T W over the upper tiles; coefs and the fold's one-element
+ * buffers.  The block products run on v_mfma_f32_32x32x2_f32, their steps dealt to the workgroup's four waves and the
+ * four partial tiles added in wave order: trip counts depend on dim alone, no atomics, two runs give the same bits.
+ * status [1] int32 is STICKY: set to 1 where a pivot of a diagonal block is not positive or not finite (the call still
+ * runs every launch and writes finite-or-NaN values), never written otherwise.  RG_EINVAL for dim < 1, dim >
+ * RG_LINUCB_MAX_DIM, a null pointer, a workspace that is short or not 4-byte aligned. */
+size_t rg_linucb_solve_blocked_workspace_bytes(int dim);
+int rg_linucb_solve_blocked(int dim, double l2_reg_lambda, float* avg_A, float* avg_b, float* sum_weight, int64_t* num_obs,
+                            float* cur_avg_A, float* cur_avg_b, float* cur_sum_weight, int64_t* cur_num_obs,
+                            float* inv_avg_A, float* coefs, float* coefs_valid_for_avg_A, int32_t* status, void* workspace,
+                            size_t workspace_bytes, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RG_LIB: another build of the same library (same-box A/B of compile-time kernel variants); default = the in-tree build
 LIB_PATH = os.environ.get("RG_LIB") or os.path.join(_HERE, "lib", "libreagent_hip.so")
 
-ABI_VERSION = 19  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
+ABI_VERSION = 20  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT = {"linear": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}
@@ -260,6 +260,8 @@ SIGNATURES = {
     "rg_dlinucb_accumulate": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3 + [c_void_p, c_sz, c_void_p]),
     "rg_dlinucb_score": (c_int, [c_void_p] * 3 + [c_d, c_int, c_int, c_int] + [c_void_p] * 5 + [c_void_p]),
     "rg_linucb_solve": (c_int, [c_int, c_d] + [c_void_p] * 12 + [c_void_p]),
+    "rg_linucb_solve_blocked_workspace_bytes": (c_sz, [c_int]),
+    "rg_linucb_solve_blocked": (c_int, [c_int, c_d] + [c_void_p] * 12 + [c_void_p, c_sz, c_void_p]),
     "rg_drlinucb_head_partials": (c_int, [c_int, c_int]),
     "rg_drlinucb_head": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_i64] + [c_void_p] * 4 + [c_void_p]),

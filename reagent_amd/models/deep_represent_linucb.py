@@ -9,10 +9,12 @@ What runs where:
                activation; in a training step also the loss and its gradients (training/cb/deep_represent_linucb_trainer.py)
   sigma, ucb : rg_linucb_score on mlp_out_with_ones, unchanged; a non-linear output activation on pred_label and ucb is
                one elementwise launch (rg_drlinucb_activate)
-  ridge solve: rg_linucb_solve, ONE launch on the device-resident buffers for d = sizes[-1] + 1 <= 128.  The reference
-               recalculates the coefficients on every training step (cur_avg_A is non-zero after every update_params,
-               :148-151): the parent's host path (six downloads, LAPACK, seven uploads) stays for d > 128 and as the
-               fallback behind the kernel's status flag.
+  ridge solve: on the device-resident buffers, no synchronisation: rg_linucb_solve, ONE launch, for d = sizes[-1] + 1
+               <= 128; rg_linucb_solve_blocked, a blocked Cholesky route in d / 32 + 3 launches on a workspace the model
+               keeps (a non-persistent buffer: it follows .to(device) and stays out of the state_dict), for 128 < d <= 512.
+               The reference recalculates the coefficients on every training step (cur_avg_A is non-zero after every
+               update_params, :148-151): the parent's host path (six downloads, LAPACK, seven uploads) stays only as the
+               fallback behind the kernels' status flag.
 
 The status flag (a pivot of the elimination was not positive or not finite) is read at the trainer's epoch end and in
 ``forward`` outside a training step; where it is set the inverse is recomputed once through the parent's inv / pinv host
@@ -83,6 +85,8 @@ class DeepRepresentLinearRegressionUCB(LinearRegressionUCB):
             assert dims[0] == input_dim and dims[-1] == sizes[-1], "mlp_layers does not map input_dim to sizes[-1]"
             self.deep_represent_layers = mlp_layers
         self.register_buffer("_solve_status", torch.zeros(1, dtype=torch.int32), persistent=False)
+        # rg_linucb_solve_blocked's workspace (d > 128): sized by the library at the first solve, then kept
+        self.register_buffer("_solve_workspace", torch.empty(0, dtype=torch.uint8), persistent=False)
 
     @property
     def _act(self) -> int:
@@ -93,16 +97,20 @@ class DeepRepresentLinearRegressionUCB(LinearRegressionUCB):
 
     # ---- the ridge solve -----------------------------------------------------------------------------------------------
     def _calculate_coefs(self) -> None:
-        """linear_regression.py:157-199: rg_linucb_solve on the buffers where they lie (d <= 128), else the parent's host
-        path.  No synchronisation: the status flag is looked at later (`check_solve_status`)."""
-        if self.input_dim > L.LINUCB_SOLVE_MAX_DIM:
-            return super()._calculate_coefs()
+        """linear_regression.py:157-199 on the buffers where they lie: rg_linucb_solve (d <= 128) or
+        rg_linucb_solve_blocked (128 < d <= 512).  No synchronisation: the status flag is looked at later
+        (`check_solve_status`)."""
         if _world_size() > 1:
             raise NotImplementedError("LinearRegressionUCB: reducing the epoch's averages over a process group (world > 1) "
                                       "is not implemented")
-        ops.linucb_solve(self.l2_reg_lambda, self.avg_A, self.avg_b, self.sum_weight, self.num_obs, self.cur_avg_A,
-                         self.cur_avg_b, self.cur_sum_weight, self.cur_num_obs, self.inv_avg_A, self._coefs,
-                         self.coefs_valid_for_avg_A, self._solve_status)
+        state = (self.avg_A, self.avg_b, self.sum_weight, self.num_obs, self.cur_avg_A, self.cur_avg_b, self.cur_sum_weight,
+                 self.cur_num_obs, self.inv_avg_A, self._coefs, self.coefs_valid_for_avg_A, self._solve_status)
+        if self.input_dim <= L.LINUCB_SOLVE_MAX_DIM:
+            ops.linucb_solve(self.l2_reg_lambda, *state)
+        else:
+            if self._solve_workspace.numel() == 0:
+                self._solve_workspace = ops.linucb_solve_blocked_workspace(self.input_dim, self.avg_A.device)
+            ops.linucb_solve_blocked(self.l2_reg_lambda, *state, self._solve_workspace)
         self._coefs_dirty = False
         self._solve_unchecked = True
 

@@ -746,6 +746,40 @@ def linucb_solve(l2_reg_lambda: float, avg_A, avg_b, sum_weight, num_obs, cur_av
                                          L.stream_ptr()))
 
 
+def linucb_solve_blocked_workspace(dim: int, device) -> torch.Tensor:
+    """the byte workspace rg_linucb_solve_blocked asks for at `dim`"""
+    n = int(L.lib().rg_linucb_solve_blocked_workspace_bytes(int(dim)))
+    if n == 0:
+        raise L.ReagentHipError(f"rg_linucb_solve_blocked does not take dim={dim} (1 <= dim <= {L.LINUCB_MAX_DIM})")
+    return torch.empty(n, dtype=torch.uint8, device=device)
+
+
+def linucb_solve_blocked(l2_reg_lambda: float, avg_A, avg_b, sum_weight, num_obs, cur_avg_A, cur_avg_b, cur_sum_weight,
+                         cur_num_obs, inv_avg_A, coefs, coefs_valid_for_avg_A, status, workspace):
+    """linucb_solve's contract for every LinUCB width (see rg_linucb_solve_blocked), in place: a blocked Cholesky route in
+    dim / 32 + 3 launches on `workspace` (linucb_solve_blocked_workspace), no synchronisation.  inv_avg_A leaves exactly
+    symmetric; status [1] int32 is sticky: 1 after a pivot that was not positive or not finite"""
+    _chk_dev(avg_A, avg_b, sum_weight, num_obs, cur_avg_A, cur_avg_b, cur_sum_weight, cur_num_obs, inv_avg_A, coefs,
+             coefs_valid_for_avg_A, status, workspace)
+    d = avg_A.shape[0]
+    for t in (avg_A, cur_avg_A, inv_avg_A, coefs_valid_for_avg_A):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (d, d)
+    for t in (avg_b, cur_avg_b, coefs):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == d
+    for t in (sum_weight, cur_sum_weight):
+        assert t.dtype == F32 and t.numel() == 1
+    for t in (num_obs, cur_num_obs):
+        assert t.dtype == torch.int64 and t.numel() == 1
+    assert status.dtype == torch.int32 and status.numel() == 1
+    assert workspace.dtype == torch.uint8 and workspace.is_contiguous()
+    _run("rg_linucb_solve_blocked", dict(d=d),
+         lambda: L.lib().rg_linucb_solve_blocked(d, float(l2_reg_lambda), L.ptr(avg_A), L.ptr(avg_b), L.ptr(sum_weight),
+                                                 L.ptr(num_obs), L.ptr(cur_avg_A), L.ptr(cur_avg_b), L.ptr(cur_sum_weight),
+                                                 L.ptr(cur_num_obs), L.ptr(inv_avg_A), L.ptr(coefs),
+                                                 L.ptr(coefs_valid_for_avg_A), L.ptr(status), L.ptr(workspace),
+                                                 workspace.numel(), L.stream_ptr()))
+
+
 def drlinucb_head_partials(batch: int, h: int) -> int:
     return int(L.lib().rg_drlinucb_head_partials(int(batch), int(h)))
 

@@ -2,8 +2,9 @@
 DeepRepresentLinearRegressionUCB trained by Adam on a weighted mse / mae / binary-cross-entropy loss of the predicted
 label, its LinUCB layer updated by hand from the MLP's output.  One step, in the reference's order:
 
-  solve      : rg_linucb_solve folds the PREVIOUS step's averages and inverts (the reference's forward recalculates the
-               coefficients on every step: cur_avg_A is non-zero after every update_params)
+  solve      : rg_linucb_solve (d <= 128) or rg_linucb_solve_blocked (128 < d <= 512) folds the PREVIOUS step's averages
+               and inverts (the reference's forward recalculates the coefficients on every step: cur_avg_A is non-zero
+               after every update_params)
   forward    : one saving forward of the MLP's stack on the chosen arm's features                 -> mlp_out [B, h]
   head       : rg_drlinucb_head -- z = [1, mlp_out], pred_label, the loss, d loss / d mlp_out and (nn_e2e) d loss /
                d linear_layer.weight
