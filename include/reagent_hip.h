@@ -869,6 +869,80 @@ int rg_linucb_solve_blocked(int dim, double l2_reg_lambda, float* avg_A, float* 
                             float* inv_avg_A, float* coefs, float* coefs_valid_for_avg_A, int32_t* status, void* workspace,
                             size_t workspace_bytes, rg_stream_t stream);
 
+/* ABI 21 — counterfactual policy evaluation (CPE) of the discrete DQN trainers on a device-resident EvaluationDataPage:
+ * reagent/evaluation/evaluation_data_page.py, doubly_robust_estimator.py, sequential_doubly_robust_estimator.py, cpe.py.
+ * Common to the five entry points: no atomics; trip counts come from the arguments (an episode's from its clamped offsets);
+ * sums are double and added in a fixed order, so two runs give the same bits; every fp32 operation named below is rounded
+ * on its own (no contraction); RG_EINVAL for a null pointer that is not marked "or NULL" and for a size out of range.
+ *
+ * rg_cpe_page_rows: the row arithmetic of EvaluationDataPage.create_from_tensors_dqn (:334-378, 408-433), one launch per
+ * validation batch.  q [batch, A] = the model outputs the policy acts on; q_cpe, reward_est [batch, M * A] = q_network_cpe
+ * (state), reward_network(state), M = 1 + the number of extra metrics (q_cpe may be NULL where M == 1); action [batch, A]
+ * (one-hot, as floats); possible_actions_mask [batch, A] or NULL (every action possible); reward [batch]; reward_boosts [A] or
+ * NULL.  logged_rewards = reward + sum_a action * boost (boost_rewards, dqn_trainer_base.py:216-241); model_propensities
+ * [batch, A] = masked_softmax(q, mask, temperature) (core/torch_utils.py:62-73, the NaN-to-0 rule of a fully masked row
+ * included; the same row code as rg_cpe_head's propensities); eval_action_idxs [batch] int64 = get_max_q_values(q, mask)[1]
+ * (first maximal q + -1e9 * (1 - mask); the same row code as rg_dqn_head's); model_rewards_for_logged_action [batch] = sum_a
+ * reward_est[:, a] * action; model_metrics_for_logged_action, model_metrics_values_for_logged_action [batch, M - 1] = the same
+ * sum over columns i A .. (i + 1) A of reward_est and q_cpe, i = 1 .. M - 1 (both unused where M == 1).  Sums over actions run
+ * left to right in fp32.
+ *
+ * rg_cpe_episode_values: EvaluationDataPage.compute_values_for_mdps (:523-540) on a page sorted by (mdp_id, sequence_number).
+ * Episode e is rows episode_offsets[e] .. episode_offsets[e + 1] - 1 ([episodes + 1] int32 in device memory, clamped to
+ * [0, rows] and to begin <= end before use).  One lane per episode walks it backwards: values[x] = column[x] + values[x + 1] *
+ * fp32(pow(gamma, double(sequence_number[x + 1] - sequence_number[x]))), the multiply and the add rounded separately; the
+ * episode's last row is column's.  column and values have pitches ld and ld_values (in floats), so a metric column of
+ * logged_metrics is scanned in place; sequence_number [rows] int64.  pow is the device library's double pow: it and the
+ * host's math.pow are each within an ulp in double, so the two fp32 factors agree unless the true value lies within 2^-29
+ * (relative) of an fp32 rounding tie; nothing closer is claimed.
+ *
+ * rg_cpe_dr_rows: the row quantities of DoublyRobustEstimator (doubly_robust_estimator.py:219-239, 266-304) and of
+ * SequentialDoublyRobustEstimator (sequential_doubly_robust_estimator.py:29-68).  model_propensities, action_mask [rows, A]
+ * contiguous; model_rewards, model_values [rows, A] with row pitches (a metric's columns are read in place); logged_propensities
+ * [rows]; logged_rewards and model_rewards_for_logged_action [rows] with pitches.  Per row, over actions left to right in fp32:
+ * target_propensity = sum p * mask; dm = sum p * model_rewards; state_value = sum p * model_values; q_logged = sum model_values
+ * * mask; then importance_weight = target_propensity / logged_propensity; ips = iw * r; dr = iw * (r - mr_logged) + dm.
+ * dm_ips_dr is [3, rows] (dm, ips, dr), so the bootstrap reads the three together.  partials: 5 * rg_cpe_dr_partials(rows)
+ * doubles (per workgroup of 256 rows); a finishing launch adds them in order into totals [5] (double): sum logged_rewards,
+ * sum dm, sum mr_logged, sum ips, sum dr.
+ *
+ * rg_cpe_sdr: the sequential-DR recurrence (:70-95), one lane per episode, backwards, fp32, g = fp32(gamma):
+ * d = state_value[j] + importance_weight[j] * ((r[j] + g * d) - q_logged[j]); e = e * g + r[j], both from 0.  doubly_robust,
+ * episode_value [episodes].  Offsets as in rg_cpe_episode_values.
+ *
+ * rg_cpe_bootstrap: bootstrapped_std_error_of_mean (cpe.py:176-191) of up to RG_CPE_BOOTSTRAP_MAX_COLUMNS columns at once.
+ * values [columns, n] fp32 with row pitch ld.  THE DRAW RECIPE: draw j (0 <= j < sample_size) of resample k (0 <= k <
+ * num_samples) takes word j % 4 of the Philox4x32-10 block with key (lo32(seed), hi32(seed)) and counter (c0, c1, c2, c3) =
+ * (j / 4, 0, k, 0) (ten rounds, multipliers 0xD2511F53 on c0 and 0xCD9E8D57 on c2, key increments 0x9E3779B9 and 0xBB67AE85;
+ * round: c' = (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0))); index = (word * n) >> 32 in 64-bit
+ * arithmetic, in [0, n) by construction; index i is drawn with probability within n / 2^32 of 1 / n.  One index stream
+ * serves every column.  One workgroup per resample (one wave where sample_size <= 256, else four), a fixed assignment of draws
+ * to lanes, per-lane double sums, a fixed-order tree; means [columns, num_samples] (double) = sum / sample_size (sample_size == 0: NaN, as np.mean of nothing).  A
+ * finishing launch writes std [columns] (double): the population standard deviation (ddof 0) of each column's means, two
+ * passes in a fixed order.  RG_EINVAL for columns outside 1 .. RG_CPE_BOOTSTRAP_MAX_COLUMNS, n < 1, ld < n, sample_size < 0,
+ * num_samples < 1. */
+#define RG_CPE_BOOTSTRAP_MAX_COLUMNS 4
+int rg_cpe_page_rows(const float* q, const float* q_cpe, const float* reward_est, const float* action,
+                     const float* possible_actions_mask, const float* reward, const float* reward_boosts, double temperature,
+                     int batch, int num_actions, int num_metrics, float* logged_rewards, float* model_propensities,
+                     int64_t* eval_action_idxs, float* model_rewards_for_logged_action,
+                     float* model_metrics_for_logged_action, float* model_metrics_values_for_logged_action,
+                     rg_stream_t stream);
+int rg_cpe_episode_values(const float* column, int64_t ld, const int64_t* sequence_number, const int32_t* episode_offsets,
+                          int episodes, int rows, double gamma, float* values, int64_t ld_values, rg_stream_t stream);
+int rg_cpe_dr_partials(int rows);
+int rg_cpe_dr_rows(const float* model_propensities, const float* action_mask, const float* model_rewards,
+                   int64_t ld_model_rewards, const float* model_values, int64_t ld_model_values,
+                   const float* logged_propensities, const float* logged_rewards, int64_t ld_logged_rewards,
+                   const float* model_rewards_for_logged_action, int64_t ld_model_rewards_for_logged_action, int rows,
+                   int num_actions, float* target_propensity, float* importance_weight, float* dm_ips_dr,
+                   float* state_value, float* q_logged, double* partials, double* totals, rg_stream_t stream);
+int rg_cpe_sdr(const float* state_value, const float* importance_weight, const float* logged_rewards,
+               int64_t ld_logged_rewards, const float* q_logged, const int32_t* episode_offsets, int episodes, int rows,
+               double gamma, float* doubly_robust, float* episode_value, rg_stream_t stream);
+int rg_cpe_bootstrap(const float* values, int64_t ld, int columns, int n, int sample_size, int num_samples, uint64_t seed,
+                     double* means, double* std, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # RG_LIB: another build of the same library (same-box A/B of compile-time kernel variants); default = the in-tree build
 LIB_PATH = os.environ.get("RG_LIB") or os.path.join(_HERE, "lib", "libreagent_hip.so")
 
-ABI_VERSION = 20  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
+ABI_VERSION = 21  # rg_abi_version() of include/reagent_hip.h this module's structs and signatures mirror
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT = {"linear": 0, "relu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4, "softplus": 5}
@@ -268,6 +268,14 @@ SIGNATURES = {
     "rg_drlinucb_activate": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "rg_cb_eval_ingest_partials": (c_int, [c_int]),
     "rg_cb_eval_ingest": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_d] + [c_void_p] * 3 + [c_void_p] * 9 + [c_void_p]),
+    "rg_cpe_page_rows": (c_int, [c_void_p] * 7 + [c_d, c_int, c_int, c_int] + [c_void_p] * 6 + [c_void_p]),
+    "rg_cpe_episode_values": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_d, c_void_p, c_i64, c_void_p]),
+    "rg_cpe_dr_partials": (c_int, [c_int]),
+    "rg_cpe_dr_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_i64,
+                               c_int, c_int] + [c_void_p] * 7 + [c_void_p]),
+    "rg_cpe_sdr": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_d, c_void_p, c_void_p,
+                           c_void_p]),
+    "rg_cpe_bootstrap": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_int, ctypes.c_uint64, c_void_p, c_void_p, c_void_p]),
     "rg_bcq_filter": (c_int, [c_void_p, c_int, c_int, c_d, c_void_p, c_void_p]),
     "rg_dqn_head_partials": (c_int, [c_int]),
     "rg_dqn_pair_wave_sums": (c_int, [c_int]),

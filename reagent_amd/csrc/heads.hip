@@ -58,17 +58,7 @@ __global__ void dqn_head_kernel(const float* __restrict__ q, const float* __rest
         }
       }
     } else {
-      for (int a = 0; a < A; ++a) {
-        const float pen = -1e9f * (1.f - next_mask[o + a]);  // ACTION_NOT_POSSIBLE_VAL * (1 - mask)
-        const float qo = (double_q ? qn_online[o + a] : qn_target[o + a]) + pen;
-        const float qt = qn_target[o + a] + pen;
-        const float key = double_q ? qo : qt;
-        if (a == 0 || key > best) {
-          best = key;
-          best_t = qt;
-          best_i = a;
-        }
-      }
+      masked_max_row(double_q ? qn_online + o : qn_target + o, qn_target + o, next_mask + o, A, best_t, best_i);
       // boost_rewards (dqn_trainer_base.py:216-241)
       if (reward_boosts)
         for (int a = 0; a < A; ++a) rb += action[o + a] * reward_boosts[a];
@@ -183,23 +173,12 @@ __global__ void cpe_head_kernel(const float* __restrict__ reward_est, const floa
         a_best = action[o + a];
         a_log = a;
       }
-    // masked softmax, pass 1: row max of x/T - (1-mask)*1e20 ; pass 2: sum of exp * mask
-    float mx = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float v = next_scores[o + a] / temperature - ((1.0f - next_mask[o + a]) * 1e20f);
-      if (a == 0 || v > mx) mx = v;
-    }
-    float den = 0.f;
-    for (int a = 0; a < A; ++a) {
-      const float v = next_scores[o + a] / temperature - ((1.0f - next_mask[o + a]) * 1e20f);
-      den += expf(v - mx) * next_mask[o + a];
-    }
+    // masked softmax (rg_dqn_head_row.h), pass 1: row max of x/T - (1-mask)*1e20 ; pass 2: sum of exp * mask
+    float mx, den;
+    masked_softmax_stats(next_scores + o, next_mask + o, A, temperature, mx, den);
     if (propensities_out)
-      for (int a = 0; a < A; ++a) {
-        const float v = next_scores[o + a] / temperature - ((1.0f - next_mask[o + a]) * 1e20f);
-        const float p = expf(v - mx) * next_mask[o + a] / den;
-        propensities_out[o + a] = p != p ? 0.f : p;
-      }
+      for (int a = 0; a < A; ++a)
+        propensities_out[o + a] = masked_softmax_p(next_scores[o + a], next_mask[o + a], temperature, mx, den);
     const float disc = gamma_exponent ? powf(gamma, gamma_exponent[b]) : gamma;
     const float nd = not_terminal[b];
     const float inv = 1.f / ((float)batch * (float)M);
@@ -215,9 +194,7 @@ __global__ void cpe_head_kernel(const float* __restrict__ reward_est, const floa
       d_reward_est[at] = 2.f * dr * inv;
       float nextq = 0.f;
       for (int a = 0; a < A; ++a) {
-        const float v = next_scores[o + a] / temperature - ((1.0f - next_mask[o + a]) * 1e20f);
-        float p = expf(v - mx) * next_mask[o + a] / den;
-        p = p != p ? 0.f : p;
+        const float p = masked_softmax_p(next_scores[o + a], next_mask[o + a], temperature, mx, den);
         nextq += q_cpe_tgt_next[om + (long)i * A + a] * p;
       }
       nextq *= nd;

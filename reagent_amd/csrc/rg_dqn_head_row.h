@@ -81,4 +81,48 @@ __device__ __forceinline__ float dqn_head_wave_sum(float loss) {
   return loss;
 }
 
+// ---- row rules shared with the evaluation page (cpe_eval.hip: rg_cpe_page_rows) ----------------------------------------------
+// get_max_q_values_with_target (dqn_trainer_base.py:33-77) over one row of A entries: the first maximal key[a] +
+// ACTION_NOT_POSSIBLE_VAL * (1 - mask[a]) (torch.max's first-index rule), its index and the target value at it (penalty
+// included).  mask == nullptr: every action possible (the penalty is then -1e9f * 0).
+__device__ __forceinline__ void masked_max_row(const float* __restrict__ key, const float* __restrict__ target,
+                                               const float* __restrict__ mask, int A, float& best_t, int& best_i) {
+  float best = 0.f;
+  best_t = 0.f;
+  best_i = 0;
+  for (int a = 0; a < A; ++a) {
+    const float pen = -1e9f * (1.f - (mask ? mask[a] : 1.f));  // ACTION_NOT_POSSIBLE_VAL * (1 - mask)
+    const float k = key[a] + pen, t = target[a] + pen;
+    if (a == 0 || k > best) {
+      best = k;
+      best_t = t;
+      best_i = a;
+    }
+  }
+}
+
+// masked_softmax (core/torch_utils.py:62-73) over one row: v = x / T - (1 - mask) * 1e20; p = exp(v - max v) * mask / sum,
+// a NaN (a fully masked row: 0 / 0) replaced by 0.  masked_softmax_stats is passes 1 and 2 (row max, denominator),
+// masked_softmax_p one entry from them.  mask == nullptr: every action possible.
+__device__ __forceinline__ float masked_softmax_logit(float x, float m, float temperature) {
+  return x / temperature - ((1.0f - m) * 1e20f);
+}
+__device__ __forceinline__ void masked_softmax_stats(const float* __restrict__ x, const float* __restrict__ mask, int A,
+                                                     float temperature, float& mx, float& den) {
+  mx = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float v = masked_softmax_logit(x[a], mask ? mask[a] : 1.f, temperature);
+    if (a == 0 || v > mx) mx = v;
+  }
+  den = 0.f;
+  for (int a = 0; a < A; ++a) {
+    const float m = mask ? mask[a] : 1.f;
+    den += expf(masked_softmax_logit(x[a], m, temperature) - mx) * m;
+  }
+}
+__device__ __forceinline__ float masked_softmax_p(float x, float m, float temperature, float mx, float den) {
+  const float p = expf(masked_softmax_logit(x, m, temperature) - mx) * m / den;
+  return p != p ? 0.f : p;
+}
+
 }  // namespace rg

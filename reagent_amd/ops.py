@@ -932,6 +932,123 @@ def cpe_head(reward_est, q_cpe, q_cpe_tgt_next, next_scores, next_mask, action, 
                                      L.stream_ptr()))
 
 
+# ---- counterfactual policy evaluation on a device-resident EvaluationDataPage (cpe_eval.hip, ABI 21) --------------------
+CPE_BOOTSTRAP_MAX_COLUMNS = 4  # RG_CPE_BOOTSTRAP_MAX_COLUMNS
+
+
+def _f32_rows(t, rows, cols):
+    """a [rows, cols] fp32 tensor or column view whose entries of a row are adjacent -> its row pitch in floats"""
+    assert t.dtype == F32 and t.dim() == 2 and t.shape == (rows, cols) and (cols == 1 or t.stride(1) == 1)
+    return int(t.stride(0)) if rows > 1 else max(int(t.stride(0)), cols)
+
+
+def cpe_page_rows(q, q_cpe, reward_est, action, possible_actions_mask, reward, reward_boosts, temperature: float,
+                  num_metrics: int):
+    """The row arithmetic of EvaluationDataPage.create_from_tensors_dqn in one launch (see rg_cpe_page_rows) -> (logged_rewards
+    [B, 1], model_propensities [B, A], eval_action_idxs [B, 1] int64, model_rewards_for_logged_action [B, 1],
+    model_metrics_for_logged_action, model_metrics_values_for_logged_action [B, M - 1] or None where M == 1)."""
+    _chk_dev(q, q_cpe, reward_est, action, possible_actions_mask, reward, reward_boosts)
+    B, A = action.shape
+    M = int(num_metrics)
+    for t in (q, action, possible_actions_mask):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == (B, A))
+    for t in (q_cpe, reward_est):
+        assert t is None or (t.dtype == F32 and t.is_contiguous() and t.shape == (B, M * A))
+    assert reward.dtype == F32 and reward.is_contiguous() and reward.numel() == B
+    assert reward_boosts is None or (reward_boosts.dtype == F32 and reward_boosts.is_contiguous() and reward_boosts.numel() == A)
+    f32 = dict(dtype=F32, device=q.device)
+    logged_rewards, mr_logged = torch.empty(B, 1, **f32), torch.empty(B, 1, **f32)
+    propensities = torch.empty(B, A, **f32)
+    idx = torch.empty(B, 1, dtype=torch.int64, device=q.device)
+    mm = torch.empty(B, M - 1, **f32) if M > 1 else None
+    mmv = torch.empty(B, M - 1, **f32) if M > 1 else None
+    _run("rg_cpe_page_rows", dict(B=B, A=A, M=M),
+         lambda: L.lib().rg_cpe_page_rows(L.ptr(q), L.ptr(q_cpe), L.ptr(reward_est), L.ptr(action),
+                                          L.ptr(possible_actions_mask), L.ptr(reward), L.ptr(reward_boosts), float(temperature),
+                                          B, A, M, L.ptr(logged_rewards), L.ptr(propensities), L.ptr(idx), L.ptr(mr_logged),
+                                          L.ptr(mm), L.ptr(mmv), L.stream_ptr()))
+    return logged_rewards, propensities, idx, mr_logged, mm, mmv
+
+
+def cpe_episode_values(column, sequence_number, episode_offsets, gamma: float, out):
+    """compute_values_for_mdps over one [N, 1] column (a view of a wider matrix is fine: its pitch is passed) of a sorted page
+    into `out` (same shape, may be a column view too); sequence_number [N] int64, episode_offsets [E + 1] int32 on the device
+    (see rg_cpe_episode_values)."""
+    _chk_dev(column, sequence_number, episode_offsets, out)
+    N = column.shape[0]
+    ld, ldv = _f32_rows(column, N, 1), _f32_rows(out, N, 1)
+    assert sequence_number.dtype == torch.int64 and sequence_number.is_contiguous() and sequence_number.numel() == N
+    assert episode_offsets.dtype == torch.int32 and episode_offsets.is_contiguous() and episode_offsets.numel() >= 2
+    E = episode_offsets.numel() - 1
+    _run("rg_cpe_episode_values", dict(N=N, E=E),
+         lambda: L.lib().rg_cpe_episode_values(L.ptr(column), ld, L.ptr(sequence_number), L.ptr(episode_offsets), E, N,
+                                               float(gamma), L.ptr(out), ldv, L.stream_ptr()))
+    return out
+
+
+def cpe_dr_rows(model_propensities, action_mask, model_rewards, model_values, logged_propensities, logged_rewards,
+                model_rewards_for_logged_action):
+    """The row quantities of the one-step and sequential doubly-robust estimators and their five totals (see rg_cpe_dr_rows)
+    -> dict(target_propensity, importance_weight, state_value, q_logged [N]; dm_ips_dr [3, N]; totals [5] float64: sum
+    logged_rewards, dm, model_rewards_for_logged_action, ips, dr).  Two launches, nothing read back."""
+    _chk_dev(model_propensities, action_mask, model_rewards, model_values, logged_propensities, logged_rewards,
+             model_rewards_for_logged_action)
+    N, A = model_propensities.shape
+    for t in (model_propensities, action_mask):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (N, A)
+    ld_mr, ld_mv = _f32_rows(model_rewards, N, A), _f32_rows(model_values, N, A)
+    ld_r, ld_mrl = _f32_rows(logged_rewards, N, 1), _f32_rows(model_rewards_for_logged_action, N, 1)
+    assert logged_propensities.dtype == F32 and logged_propensities.is_contiguous() and logged_propensities.numel() == N
+    dev = model_propensities.device
+    f32 = dict(dtype=F32, device=dev)
+    out = dict(target_propensity=torch.empty(N, **f32), importance_weight=torch.empty(N, **f32),
+               dm_ips_dr=torch.empty(3, N, **f32), state_value=torch.empty(N, **f32), q_logged=torch.empty(N, **f32),
+               totals=torch.empty(5, dtype=torch.float64, device=dev))
+    P = int(L.lib().rg_cpe_dr_partials(N))
+    if P == 0:
+        raise L.ReagentHipError(f"rg_cpe_dr_rows does not take rows={N} (rows >= 1)")
+    partials = torch.empty(5 * P, dtype=torch.float64, device=dev)
+    _run("rg_cpe_dr_rows", dict(N=N, A=A),
+         lambda: L.lib().rg_cpe_dr_rows(L.ptr(model_propensities), L.ptr(action_mask), L.ptr(model_rewards), ld_mr,
+                                        L.ptr(model_values), ld_mv, L.ptr(logged_propensities), L.ptr(logged_rewards), ld_r,
+                                        L.ptr(model_rewards_for_logged_action), ld_mrl, N, A, L.ptr(out["target_propensity"]),
+                                        L.ptr(out["importance_weight"]), L.ptr(out["dm_ips_dr"]), L.ptr(out["state_value"]),
+                                        L.ptr(out["q_logged"]), L.ptr(partials), L.ptr(out["totals"]), L.stream_ptr()))
+    return out
+
+
+def cpe_sdr(state_value, importance_weight, logged_rewards, q_logged, episode_offsets, gamma: float):
+    """The sequential doubly-robust recurrence, one lane per episode (see rg_cpe_sdr) -> (doubly_robust [E], episode_value [E])"""
+    _chk_dev(state_value, importance_weight, logged_rewards, q_logged, episode_offsets)
+    N = state_value.numel()
+    for t in (state_value, importance_weight, q_logged):
+        assert t.dtype == F32 and t.is_contiguous() and t.numel() == N
+    ld_r = _f32_rows(logged_rewards, N, 1)
+    assert episode_offsets.dtype == torch.int32 and episode_offsets.is_contiguous() and episode_offsets.numel() >= 2
+    E = episode_offsets.numel() - 1
+    dr = torch.empty(E, dtype=F32, device=state_value.device)
+    ev = torch.empty(E, dtype=F32, device=state_value.device)
+    _run("rg_cpe_sdr", dict(N=N, E=E),
+         lambda: L.lib().rg_cpe_sdr(L.ptr(state_value), L.ptr(importance_weight), L.ptr(logged_rewards), ld_r, L.ptr(q_logged),
+                                    L.ptr(episode_offsets), E, N, float(gamma), L.ptr(dr), L.ptr(ev), L.stream_ptr()))
+    return dr, ev
+
+
+def cpe_bootstrap(values, sample_size: int, num_samples: int, seed: int):
+    """Bootstrap resampling of the C <= 4 rows of values [C, n] with one index stream (see rg_cpe_bootstrap, which states the
+    draw recipe) -> (means [C, num_samples], std [C]), float64 on the device."""
+    _chk_dev(values)
+    assert values.dtype == F32 and values.dim() == 2 and values.stride(1) == 1
+    C, n = values.shape
+    ld = int(values.stride(0)) if C > 1 else max(int(values.stride(0)), n)
+    means = torch.empty(C, int(num_samples), dtype=torch.float64, device=values.device)
+    std = torch.empty(C, dtype=torch.float64, device=values.device)
+    _run("rg_cpe_bootstrap", dict(C=C, n=n, S=int(sample_size), K=int(num_samples)),
+         lambda: L.lib().rg_cpe_bootstrap(L.ptr(values), ld, C, n, int(sample_size), int(num_samples),
+                                          int(seed) & 0xFFFFFFFFFFFFFFFF, L.ptr(means), L.ptr(std), L.stream_ptr()))
+    return means, std
+
+
 def c51_head(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal, gamma,
              gamma_exponent, support, qmin, qmax, num_atoms, maxq, dq, loss_partials, all_q=None):
     _chk_dev(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal, gamma_exponent,

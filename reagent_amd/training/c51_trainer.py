@@ -72,6 +72,8 @@ class C51Trainer(QStepCore):
         ops.reduce_sum(self._loss_partials, B, 1.0, self._loss)
         self.all_q_values = self._all_q
 
+    _cpe_evaluation_served = False  # validation_step refuses by name: C51 trains no CPE networks
+
     def train_step_gen(self, training_batch: rlt.DiscreteDqnInput, batch_idx: int):
         loss = self._hip_loss(training_batch)
         # c51_trainer.py:178: reported every `log_every_n_steps` batches of the driving trainer (50 without one)

@@ -230,6 +230,9 @@ class DiscreteCRRTrainer(NativeStepMixin, DQNTrainerBaseLightning):
         return None  # discount_tensor = full_like(rewards, gamma) (:305)
 
     # ---- reference surface -----------------------------------------------------------------------
+    def validation_step(self, batch, batch_idx):
+        raise NotImplementedError("DiscreteCRRTrainer.validation_step: CPE (EvaluationDataPage) is built for DQNTrainer and QRDQNTrainer only")
+
     def train_step_gen(self, training_batch: rlt.DiscreteDqnInput, batch_idx: int):
         """IMPORTANT: the action of a DiscreteDqnInput is one-hot (DiscreteDqnInputMaker)."""
         self._check_input(training_batch)

@@ -529,8 +529,57 @@ class QStepCore(NativeStepMixin, DQNTrainerBaseLightning):
         self.all_batches_processed += 1
         self._update_pending = False
 
+    # ---- counterfactual policy evaluation (dqn_trainer_base.py:454-509; evaluation/, csrc/cpe_eval.hip) --------------------------
+    _cpe_evaluation_served = True  # DQNTrainer and QRDQNTrainer; C51Trainer says False
+
+    def _check_cpe_evaluation(self):
+        """the named refusals of validation_step / EvaluationDataPage.create_from_tensors_dqn"""
+        if not self._cpe_evaluation_served:
+            raise NotImplementedError(f"{type(self).__name__}.validation_step: CPE (EvaluationDataPage) is built for "
+                                      "DQNTrainer and QRDQNTrainer only")
+        if self._dp_world > 1:
+            raise NotImplementedError("CPE (validation_step / EvaluationDataPage) with data parallel world > 1 is not built: "
+                                      "the page is gathered on one device")
+        if getattr(self, "reward_network", None) is None or getattr(self, "q_network_cpe", None) is None:
+            raise RuntimeError(
+                f"{type(self).__name__} was built without CPE networks (evaluation=EvaluationParameters("
+                "calc_cpe_in_training=False)): validation_step needs reward_network and q_network_cpe, which only "
+                "calc_cpe_in_training=True trains")
+
+    def _cpe_model_outputs(self, state):
+        """the action scores the evaluated policy acts on (get_detached_model_outputs(state)[0] without the target network's
+        forward): one non-saving forward of the q_network's stack"""
+        return self.q_network(state)
+
+    @torch.no_grad()
     def validation_step(self, batch, batch_idx):
-        raise NotImplementedError("CPE / EvaluationDataPage is outside the hot path (SURVEY.md §3.4)")
+        """dqn_trainer_base.py:485-492.  Returns an EvaluationDataPage ON THE DEVICE (the reference moves it to the host)."""
+        from ..evaluation.evaluation_data_page import EvaluationDataPage
+
+        self._check_cpe_evaluation()
+        if isinstance(batch, dict):
+            batch = rlt.DiscreteDqnInput.from_dict(batch)
+        return EvaluationDataPage.create_from_training_batch(batch, self)
+
+    def gather_eval_data(self, validation_step_outputs):
+        """dqn_trainer_base.py:454-483: append, sort, compute_values, validate, all on the pages' device.  The reference's
+        round trip of the model to the host and back (`self.cpu()` ... `self.cuda()`) is not made."""
+        eval_data = None
+        for edp in validation_step_outputs:
+            eval_data = edp if eval_data is None else eval_data.append(edp)
+        if eval_data is not None and eval_data.mdp_id is not None:
+            eval_data = eval_data.sort()
+            eval_data = eval_data.compute_values(self.gamma)
+            eval_data.validate()
+        return eval_data
+
+    def validation_epoch_end(self, valid_step_outputs):
+        """dqn_trainer_base.py:494-509"""
+        self._check_cpe_evaluation()
+        eval_data = self.gather_eval_data(valid_step_outputs)
+        if eval_data is not None and eval_data.mdp_id is not None:
+            cpe_details = self.evaluator.evaluate_post_training(eval_data)
+            self.reporter.log(cpe_details=cpe_details)
 
 
 class DQNTrainer(QStepCore):

@@ -5,7 +5,8 @@ CPE (reward network / q_network_cpe heads, :243-452) is
 DQN, QR-DQN and discrete CRR trainers (`_CpeEngine` in dqn_trainer.py, its two networks held as plumbing.TrainableNet;
 `_CpeEngine.segment` is the CPE part of their train_step_gen); the trainers that do not run it yet reject
 calc_cpe_in_training=True at construction rather than silently skipping it.  The Evaluator /
-EvaluationDataPage side (:454-509) is control plane and stays out.
+EvaluationDataPage side (:454-509: validation_step, gather_eval_data, validation_epoch_end) is QStepCore's, for DQNTrainer
+and QRDQNTrainer, on a device-resident page (reagent_amd/evaluation, csrc/cpe_eval.hip).
 """
 from typing import Dict, List, Optional
 
@@ -100,7 +101,7 @@ class DQNTrainerBaseLightning(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningM
         return rewards + reward_boosts
 
     def _initialize_cpe(self, reward_network, q_network_cpe, q_network_cpe_target, optimizer) -> None:
-        """dqn_trainer_base.py:243-311 without the Evaluator object (evaluation pages are control plane)."""
+        """dqn_trainer_base.py:243-311"""
         if not self.calc_cpe_in_training:
             self.reward_network = None
             return
@@ -116,6 +117,11 @@ class DQNTrainerBaseLightning(DQNTrainerMixin, RLTrainerMixin, ReAgentLightningM
         num_output_nodes = len(self.metrics_to_score) * self.num_actions
         self.register_buffer("reward_idx_offsets",
                              torch.arange(0, num_output_nodes, self.num_actions, dtype=torch.long))
+        from ..evaluation.evaluator import Evaluator
+
+        reward_stripped_metrics_to_score = self.metrics_to_score[:-1] if len(self.metrics_to_score) > 1 else None
+        self.evaluator = Evaluator(self._actions, self.rl_parameters.gamma, self,
+                                   metrics_to_score=reward_stripped_metrics_to_score)
 
     def _configure_cpe_optimizers(self):
         """dqn_trainer_base.py:313-336"""

@@ -158,6 +158,9 @@ class ParametricDQNTrainer(PanelCriticMixin, NativeStepMixin, DQNTrainerMixin, R
         self._e[which].backward(dq, xt, grad_out)
 
     # ---- reference surface ---------------------------------------------------------------------------
+    def validation_step(self, batch, batch_idx):
+        raise NotImplementedError("ParametricDQNTrainer.validation_step: CPE (EvaluationDataPage) is built for DQNTrainer and QRDQNTrainer only")
+
     def train_step_gen(self, training_batch: rlt.ParametricDqnInput, batch_idx: int):
         self._check_input(training_batch)
         b = training_batch

@@ -145,6 +145,10 @@ class QRDQNTrainer(QStepCore):
     def _cpe_scores_for_logging(self):
         return self.all_q_values
 
+    def _cpe_model_outputs(self, state):
+        """qrdqn_trainer.py:220-227, the online half: q_network(state).mean(dim=2)"""
+        return self.q_network(state).mean(dim=2)
+
     def train_step_gen(self, training_batch: rlt.DiscreteDqnInput, batch_idx: int):
         self._check_input(training_batch)
         loss = self._hip_loss(training_batch)
