@@ -943,6 +943,56 @@ int rg_cpe_sdr(const float* state_value, const float* importance_weight, const f
 int rg_cpe_bootstrap(const float* values, int64_t ld, int columns, int n, int sample_size, int num_samples, uint64_t seed,
                      double* means, double* std, rg_stream_t stream);
 
+/* ABI 22 — the weighted sequential doubly-robust and MAGIC estimators' row and episode arithmetic on a sorted, device-resident
+ * EvaluationDataPage (reagent/evaluation/weighted_sequential_doubly_robust_estimator.py:27-155, 275-353; arXiv 1604.00923
+ * sections 5, 7, 8).  Everything of the reference's estimate() except the quadratic program over the j-step weights, which
+ * stays on the host: rg_cpe_wsdr leaves j_step_returns, infinite_step_returns, the covariance of the j-step returns and the
+ * mean episode value in `out`, J + G + J * J + 1 doubles, read back once.
+ *
+ * Inputs.  model_propensities, action_mask [rows, A] contiguous; model_values [rows, A] with row pitch ld_model_values (a
+ * metric's columns are read in place); logged_propensities [rows]; logged_rewards [rows] with pitch ld_logged_rewards (a
+ * set_metric_as_reward page's column); all fp32 in device memory.  episode_offsets [episodes + 1] int32 in device memory as in
+ * rg_cpe_episode_values (clamped to [0, rows] and to begin <= end before use; an episode longer than `longest` is cut to it).
+ * longest = T, the longest episode.  j_steps [J] and subset_offsets [G + 1] int32 are HOST arrays, copied into the launch
+ * arguments: j_steps already reduced to -1 .. T - 1 (the reference's inf is T - 1), J <= RG_CPE_WSDR_MAX_J_STEPS; subset g is
+ * episodes subset_offsets[g] .. subset_offsets[g + 1] - 1 (non-decreasing, inside [0, episodes]; G <= RG_CPE_WSDR_MAX_SUBSETS;
+ * n_g = its length).  An episode in no subset (:118-119's float interval can leave the last one out) still counts in the whole
+ * set.  J == 1 (weighted DR) takes no subsets (subset_offsets and G are ignored) and computes no covariance: `out` is then
+ * j_step_returns[0], the mean episode value at out[1], and its whole-set column sums are added over min(episodes, 32) even
+ * runs of episodes in run order.
+ *
+ * All arithmetic is double on the fp32 inputs, each operation rounded on its own (no contraction), no atomics, a fixed order
+ * of adds: two runs give the same bits.  Padding is virtual: a step t >= len_e has reward, state value and logged q 0 and raw
+ * weight 0; nothing of size episodes * T is stored.  The launches, all on `stream`, nothing synchronised in between:
+ *  1. rows, a thread per row, over actions left to right: ratio = (sum p * mask) / logged_p; sv = sum p * mv; ql = sum mv * mask.
+ *  2. cumulative weights, a lane per episode, forwards: w_raw[row] = product of ratio up to that row (:72-73).
+ *  3. column sums, a thread per step t (neighbouring lanes read neighbouring rows of one episode), a grid row per subset:
+ *     S[g, t] = sum of w_raw over the subset's episodes longer than t, in episode order; then S[t] = sum_g S[g, t] in subset
+ *     order plus the left-out episodes in episode order, and disc[t] = pow(gamma, (double)t) (:86-88, np.logspace).
+ *  4. returns, a lane per episode walking its rows once.  With a set's column sums S and size n (normalize_importance_weights,
+ *     :275-289): wn[t] = self_normalize ? (S[t] == 0 ? 1 / n : w_raw[t] / S[t]) : w_raw[t] / n; wprev[0] = 1 / n, wprev[t] =
+ *     wn[t - 1]; P_t = sum_{s <= t} disc[s] * (wn[s] * r[s] - wn[s] * ql[s] + wprev[s] * sv[s]), s ascending, P_-1 = 0;
+ *     ret[j, e] = P_min(j_steps[j], len - 1) + (j_steps[j] + 1 < len ? disc[j + 1] * wprev[j + 1] * sv[j + 1] : 0)
+ *     (calculate_step_return, :291-343).  ret is [J + 1, episodes]; its last row is the episode value sum_t disc[t] * r[t].
+ *     inf_ret[e] is the same with j = T - 1 and the episode's own subset's S[g, .] and n_g; 0 for an episode in no subset.
+ *  5. moments: j_step_returns[j] = sum_e ret[j, e]; infinite_step_returns[g] = sum_{e in g} inf_ret[e]; the mean of the
+ *     episode-value row; C[j, k] = sum_e (ret[j, e] - m_j) (ret[k, e] - m_k) / (episodes - 1) with m = the row means, as
+ *     np.cov does it (:228).  One workgroup per sum and per pair k >= j: a strided lane sum in episode order (lane i adds
+ *     i, i + 256, ...), a fixed LDS tree; C[k, j] is the same double as C[j, k].  episodes == 1 gives 0 / 0 = NaN as np.cov.
+ * out = j_step_returns [J], infinite_step_returns [G], C [J, J] row-major, mean episode value [1] (J == 1: [2], see above).
+ * workspace: rg_cpe_wsdr_workspace_bytes(rows, episodes, longest, J, G) bytes of device memory, 0 for arguments rg_cpe_wsdr
+ * refuses.  RG_EINVAL for a null pointer, J, G, episodes or rows < 1 (G only where J > 1), J or G beyond its maximum, episodes >
+ * rows, longest < 1 or > rows, num_actions < 1, a j_step outside -1 .. T - 1, subset offsets that decrease or leave [0,
+ * episodes], a pitch below its row, a workspace too small. */
+#define RG_CPE_WSDR_MAX_J_STEPS 32
+#define RG_CPE_WSDR_MAX_SUBSETS 32
+size_t rg_cpe_wsdr_workspace_bytes(int rows, int episodes, int longest, int num_j_steps, int num_subsets);
+int rg_cpe_wsdr(const float* model_propensities, const float* action_mask, const float* model_values, int64_t ld_model_values,
+                const float* logged_propensities, const float* logged_rewards, int64_t ld_logged_rewards,
+                const int32_t* episode_offsets, int rows, int num_actions, int episodes, int longest, double gamma,
+                int self_normalize, const int32_t* j_steps, int num_j_steps, const int32_t* subset_offsets, int num_subsets,
+                void* workspace, size_t workspace_bytes, double* ret, double* out, rg_stream_t stream);
+
 /* Batch-constrained q-learning (reagent/training/dqn_trainer.py:209-215 with
  * get_valid_actions_from_imitator, reagent/training/imitator_training.py:12-25): mask [B, A] (in place)
  * *= (softmax(imitator_logits)[b, a] / max_a softmax(imitator_logits)[b, :] >= drop_threshold). */

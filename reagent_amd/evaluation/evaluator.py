@@ -1,10 +1,12 @@
 """reagent/evaluation/evaluator.py: Evaluator for the discrete DQN trainers, on a device-resident EvaluationDataPage.
 
-NOT the reference's result in two places, both by design of this package's scope:
-  * ``score_cpe`` leaves ``weighted_doubly_robust`` and ``magic`` as None: weighted sequential DR and MAGIC
-    (weighted_sequential_doubly_robust_estimator.py: host numpy plus scipy.optimize) are not built;
-  * ``evaluate_post_training`` therefore returns every CpeEstimateSet after ``fill_empty_with_zero()``, so those two read
-    0.0 and ``CpeEstimateSet.log`` / ``check_estimates_exist`` work on what is returned.
+NOT the reference's result in one place: weighted sequential DR and MAGIC are OPT-IN.  ``score_cpe`` fills
+``weighted_doubly_robust`` and ``magic`` (weighted_sequential_doubly_robust_estimator.py: rg_cpe_wsdr plus a numpy quadratic
+program) only where ``SCORE_WEIGHTED_ESTIMATORS`` is true, on the class or on an instance
+(``trainer.evaluator.SCORE_WEIGHTED_ESTIMATORS = True``); it is False by default, and then both stay None, nothing of
+that estimator runs and nothing is drawn from any generator.  ``evaluate_post_training`` returns every CpeEstimateSet after
+``fill_empty_with_zero()``, so fields left None read 0.0 and ``CpeEstimateSet.log`` / ``check_estimates_exist`` work on what
+is returned.  A page of fewer than four episodes has no MAGIC estimate: score_cpe warns and leaves ``magic`` None.
 The observer notification of the reference (``@observable``) is not built: the trainer hands the CpeDetails to its reporter.
 """
 import logging
@@ -16,6 +18,7 @@ from .cpe import CpeDetails, CpeEstimateSet
 from .doubly_robust_estimator import DoublyRobustEstimator
 from .evaluation_data_page import EvaluationDataPage
 from .sequential_doubly_robust_estimator import SequentialDoublyRobustEstimator
+from .weighted_sequential_doubly_robust_estimator import WeightedSequentialDoublyRobustEstimator
 
 logger = logging.getLogger(__name__)
 
@@ -52,6 +55,7 @@ def get_metrics_to_score(metric_reward_values: Optional[Dict[str, float]]) -> Li
 
 class Evaluator:
     NUM_J_STEPS_FOR_MAGIC_ESTIMATOR = 25
+    SCORE_WEIGHTED_ESTIMATORS = False  # settable on an instance: score_cpe then fills weighted_doubly_robust and magic
 
     def __init__(self, action_names, gamma, model, metrics_to_score=None) -> None:
         self.action_names = action_names
@@ -62,10 +66,11 @@ class Evaluator:
 
         self.doubly_robust_estimator = DoublyRobustEstimator()
         self.sequential_doubly_robust_estimator = SequentialDoublyRobustEstimator(gamma)
+        self.weighted_sequential_doubly_robust_estimator = WeightedSequentialDoublyRobustEstimator(gamma)
 
     def evaluate_post_training(self, edp: EvaluationDataPage) -> CpeDetails:
         """evaluator.py:73-117.  Every estimate set is returned after fill_empty_with_zero(): weighted_doubly_robust and
-        magic, which score_cpe leaves None, read 0.0."""
+        magic read 0.0 where score_cpe leaves them None (SCORE_WEIGHTED_ESTIMATORS unset)."""
         cpe_details = CpeDetails()
 
         cpe_details.reward_estimates = self.score_cpe("Reward", edp).fill_empty_with_zero()
@@ -94,16 +99,32 @@ class Evaluator:
         return cpe_details
 
     def score_cpe(self, metric_name, edp: EvaluationDataPage):
-        """evaluator.py:119-143 without the weighted sequential DR and MAGIC estimates: both stay None here."""
+        """evaluator.py:119-143; the weighted sequential DR and MAGIC estimates only where SCORE_WEIGHTED_ESTIMATORS is set,
+        else both stay None."""
         direct_method, inverse_propensity, doubly_robust = self.doubly_robust_estimator.estimate(edp)
         sequential_doubly_robust = self.sequential_doubly_robust_estimator.estimate(edp)
+        weighted_doubly_robust = magic = None
+        if self.SCORE_WEIGHTED_ESTIMATORS:
+            weighted_doubly_robust = self.weighted_sequential_doubly_robust_estimator.estimate(
+                edp, num_j_steps=1, whether_self_normalize_importance_weights=True
+            )
+            try:
+                magic = self.weighted_sequential_doubly_robust_estimator.estimate(
+                    edp,
+                    num_j_steps=Evaluator.NUM_J_STEPS_FOR_MAGIC_ESTIMATOR,
+                    whether_self_normalize_importance_weights=True,
+                )
+            except ValueError as e:
+                if "at least 4 episodes" not in str(e):
+                    raise
+                logger.warning("No MAGIC estimate for %s: %s", metric_name, e)
         return CpeEstimateSet(
             direct_method=direct_method,
             inverse_propensity=inverse_propensity,
             doubly_robust=doubly_robust,
             sequential_doubly_robust=sequential_doubly_robust,
-            weighted_doubly_robust=None,
-            magic=None,
+            weighted_doubly_robust=weighted_doubly_robust,
+            magic=magic,
         )
 
     def get_target_distribution_error(self, actions, target_distribution, actual_distribution):

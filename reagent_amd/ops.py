@@ -1049,6 +1049,51 @@ def cpe_bootstrap(values, sample_size: int, num_samples: int, seed: int):
     return means, std
 
 
+# ---- weighted sequential DR and MAGIC: row and episode arithmetic (cpe_wsdr.hip, ABI 22) ---------------------------------
+CPE_WSDR_MAX_J_STEPS = 32  # RG_CPE_WSDR_MAX_J_STEPS
+CPE_WSDR_MAX_SUBSETS = 32  # RG_CPE_WSDR_MAX_SUBSETS
+
+
+def cpe_wsdr(model_propensities, action_mask, model_values, logged_propensities, logged_rewards, episode_offsets,
+             longest: int, gamma: float, self_normalize: bool, j_steps, subset_offsets=None):
+    """The device part of WeightedSequentialDoublyRobustEstimator.estimate on a sorted page (see rg_cpe_wsdr): j_steps (a
+    sequence of J ints in -1 .. longest - 1) and subset_offsets (G + 1 ints, None where J == 1) are host values.
+    -> (ret [J + 1, E] float64 on the device: the per-episode j-step returns and, last, the episode values;
+        out float64 on the device: j_step_returns [J], infinite_step_returns [G], covariance [J, J], mean episode value [1]
+        (J == 1: j_step_returns[0] and the mean episode value)).  The launches go on the current stream; nothing is read back."""
+    _chk_dev(model_propensities, action_mask, model_values, logged_propensities, logged_rewards, episode_offsets)
+    N, A = model_propensities.shape
+    for t in (model_propensities, action_mask):
+        assert t.dtype == F32 and t.is_contiguous() and t.shape == (N, A)
+    ld_mv, ld_r = _f32_rows(model_values, N, A), _f32_rows(logged_rewards, N, 1)
+    assert logged_propensities.dtype == F32 and logged_propensities.is_contiguous() and logged_propensities.numel() == N
+    assert episode_offsets.dtype == torch.int32 and episode_offsets.is_contiguous() and episode_offsets.numel() >= 2
+    E = episode_offsets.numel() - 1
+    js = [int(j) for j in j_steps]
+    J = len(js)
+    so = [int(b) for b in subset_offsets] if subset_offsets is not None else []
+    G = len(so) - 1 if J > 1 else 0
+    dev = model_propensities.device
+    nbytes = int(L.lib().rg_cpe_wsdr_workspace_bytes(N, E, int(longest), J, G))
+    if nbytes == 0:
+        raise L.ReagentHipError(f"rg_cpe_wsdr does not take rows={N} episodes={E} longest={longest} j_steps={J} subsets={G} "
+                                f"(1 <= episodes <= rows, 1 <= longest <= rows, 1 <= j_steps <= {CPE_WSDR_MAX_J_STEPS}, "
+                                f"1 <= subsets <= {CPE_WSDR_MAX_SUBSETS} where j_steps > 1)")
+    workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    ret = torch.empty(J + 1, E, dtype=torch.float64, device=dev)
+    out = torch.empty(J + G + J * J + 1 if J > 1 else 2, dtype=torch.float64, device=dev)
+    c_js = (ctypes.c_int32 * J)(*js)
+    c_so = (ctypes.c_int32 * len(so))(*so) if J > 1 else None
+    _run("rg_cpe_wsdr", dict(N=N, A=A, E=E, T=int(longest), J=J, G=G),
+         lambda: L.lib().rg_cpe_wsdr(L.ptr(model_propensities), L.ptr(action_mask), L.ptr(model_values), ld_mv,
+                                     L.ptr(logged_propensities), L.ptr(logged_rewards), ld_r, L.ptr(episode_offsets), N, A, E,
+                                     int(longest), float(gamma), int(bool(self_normalize)),
+                                     ctypes.cast(c_js, ctypes.c_void_p), J,
+                                     ctypes.cast(c_so, ctypes.c_void_p) if c_so is not None else None, G,
+                                     L.ptr(workspace), nbytes, L.ptr(ret), L.ptr(out), L.stream_ptr()))
+    return ret, out
+
+
 def c51_head(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal, gamma,
              gamma_exponent, support, qmin, qmax, num_atoms, maxq, dq, loss_partials, all_q=None):
     _chk_dev(q, qn_online, qn_target, action, next_mask, reward, reward_boosts, not_terminal, gamma_exponent,
