@@ -1248,6 +1248,66 @@ int rg_sched_tick_many(double* const* scheds, int n, rg_stream_t stream);
 /* SoftUpdate.step, reagent/optimizer/soft_update.py:60-70: tgt = tau*src + (1-tau)*tgt */
 int rg_soft_update(float* target, const float* source, int64_t n, double tau, rg_stream_t stream);
 
+/* World model: MDN-RNN (reagent/models/mdn_rnn.py, reagent/training/world_model/mdnrnn_trainer.py).  Additive symbols: the
+ * ABI number does not move.  All fp32 (RG_PREC_F32 throughout), every array contiguous unless a pitch is named.
+ *
+ * rg_lstm_forward: one layer of nn.LSTM(num_layers = L), sequence first, unidirectional, gate order i, f, g, o
+ * (mdn_rnn.py:32-36, :72), all seq_len steps in one launch.  xproj [T, B, 4H] = x * W_ih^T + b_ih for all steps at once
+ * (rg_fc_forward over T * B rows, RG_ACT_LINEAR); w_hh [4H, H]; b_hh [4H] or NULL; h0, c0 [B, H] or NULL (zeros).
+ *   pre = xproj[t] + b_hh + h_{t-1} * w_hh^T;  i, f, o = sigmoid, g = tanh;  c_t = f * c_{t-1} + i * g;  h_t = o * tanh(c_t)
+ * Outputs: h_all, c_all [T, B, H]; gates [T, B, 4H] after their non-linearities, or NULL for a forward that saves nothing
+ * for a backward (same h_all bits).  A workgroup owns 32 batch rows for the whole sequence (h_{t-1} in LDS, two images);
+ * its four waves own the hidden units in tiles of 32, each holding the four gates' accumulators of its units.  The product
+ * is a k-ordered fp32 fma chain over H (v_mfma_f32_32x32x2_f32, zero-padded to a multiple of 32); the gate arithmetic runs
+ * in double on it and is rounded once per stored value; tanh(c_t) is taken of the stored fp32 c_t.  A row's bits depend on
+ * that row alone, trip counts on H alone; no atomics.
+ *
+ * rg_lstm_backward: the same layer in reverse (autograd's backward of the lines above).  dh_all [T, B, H] = the gradient
+ * arriving from above at every step (the gradient with respect to the final h_n, where there is one, added into its last
+ * step by the caller); gates, c_all, c0, w_hh as the forward had them.  Outputs: dgates [T, B, 4H] = d loss / d pre; dh0,
+ * dc0 [B, H] (nullable).  The weight, bias and input gradients are the caller's: dW_ih = dgates^T * x and db_ih = db_hh =
+ * the column sums (rg_fc_wgrad over T * B rows), dW_hh = dgates[1:]^T * h_all[:-1] (plus dgates[0]^T * h0), dx = dgates *
+ * W_ih (rg_fc_dgrad).  Per step: the element-wise part in double, then dh_rec = dgates[t] * w_hh on the fp32 MFMA, K = 4H,
+ * staged through LDS one gate at a time.
+ *
+ * Both: RG_EINVAL for seq_len, batch or hidden < 1 or a null pointer not marked nullable; RG_EUNSUPPORTED for hidden >
+ * RG_LSTM_MAX_HIDDEN or seq_len * batch >= 2^29. */
+#define RG_LSTM_MAX_HIDDEN 256
+#define RG_LSTM_MAX_LAYERS 4 /* the host's limit on num_hidden_layers (a launch is one layer) */
+int rg_lstm_forward(const float* xproj, const float* w_hh, const float* b_hh, const float* h0, const float* c0, int seq_len,
+                    int batch, int hidden, float* h_all, float* c_all, float* gates, rg_stream_t stream);
+int rg_lstm_backward(const float* dh_all, const float* gates, const float* c_all, const float* c0, const float* w_hh,
+                     int seq_len, int batch, int hidden, float* dgates, float* dh0, float* dc0, rg_stream_t stream);
+
+/* rg_mdn_head: the mixture-density head over n = T * B rows.  z [n, (2S + 1) G + 2] (pitch ldz) = gmm_linear's output:
+ * mus [G, S], log sigmas [G, S], mixture logits [G], reward, not_terminal logit (mdn_rnn.py:75-92).  next_state [n, S],
+ * reward [n], not_terminal [n].  With rows = n - first_row (fit_only_one_next_step passes (T - 1) * B: the last step):
+ *   gmm = next_state_loss_weight * mean over the rows of -log sum_g pi_g N(next_state | mu_g, sigma_g)  (gmm_loss, :188-233)
+ *   bce = not_terminal_loss_weight * mean binary_cross_entropy_with_logits(z[-1], not_terminal)
+ *   mse = reward_loss_weight * mean (z[-2] - reward)^2
+ *   loss = gmm / (S + 2) + bce + mse with divide_by_state_dim, gmm + bce + mse without  (mdnrnn_trainer.py:164-177)
+ * Outputs: losses [4] = gmm, bce, mse, loss; dz [n, .] (pitch lddz) = d loss / d z, rows before first_row exactly zero;
+ * sigmas [n, G, S] = exp(log sigma) and logpi [n, G] = log_softmax(logits) for all n rows (each nullable).  partials:
+ * 3 * rg_mdn_head_partials(n) doubles of scratch.  One wave per row; a row's arithmetic is double on the fp32 inputs,
+ * rounded once where it is stored; the three sums leave as per-workgroup partials in double and a finishing launch adds
+ * them in a fixed order and rounds once.  No atomics: two runs give the same bits.
+ * rg_mdn_outputs: the same sigmas and logpi (bit for bit) without targets: what MDNRNN.forward returns.
+ * rg_mdn_gmm_nll: gmm_loss(batch, mus, sigmas, logpi, reduce = False) on its own arguments as they are (sigmas, not their
+ * logarithms; logpi not normalised again): nll [n] = -log_prob.
+ * All: RG_EINVAL for n, G or S < 1, a null pointer not marked nullable, a pitch below the row, first_row outside [0, n);
+ * RG_EUNSUPPORTED for G > RG_MDN_MAX_GAUSSIANS or S > RG_MDN_MAX_STATE_DIM. */
+#define RG_MDN_MAX_GAUSSIANS 32
+#define RG_MDN_MAX_STATE_DIM 512
+int rg_mdn_head_partials(int n);
+int rg_mdn_head(const float* z, int64_t ldz, const float* next_state, const float* reward, const float* not_terminal,
+                double next_state_loss_weight, double not_terminal_loss_weight, double reward_loss_weight,
+                int divide_by_state_dim, int first_row, int n, int num_gaussians, int state_dim, float* dz, int64_t lddz,
+                float* sigmas, float* logpi, double* partials, float* losses, rg_stream_t stream);
+int rg_mdn_outputs(const float* z, int64_t ldz, int n, int num_gaussians, int state_dim, float* sigmas, float* logpi,
+                   rg_stream_t stream);
+int rg_mdn_gmm_nll(const float* batch, const float* mus, const float* sigmas, const float* logpi, int n, int num_gaussians,
+                   int state_dim, float* nll, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ PG_MAX_ACTIONS = 256  # RG_PG_MAX_ACTIONS: rg_pg_head's limit on A
 PG_REINFORCE, PG_REINFORCE_OFF_POLICY, PG_PPO = 0, 1, 2  # RG_PG_*: rg_pg_head's modes
 LINUCB_MAX_DIM = 512  # RG_LINUCB_MAX_DIM: the LinUCB kernels' limit on the feature dimension
 LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (the matrix lives in one workgroup's registers)
+LSTM_MAX_HIDDEN, LSTM_MAX_LAYERS = 256, 4  # RG_LSTM_MAX_HIDDEN, RG_LSTM_MAX_LAYERS: the LSTM kernels' limits
+MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
 CB_LOSS = {"mse": 0, "mae": 1, "cross_entropy": 2}  # RG_CB_LOSS_*: rg_drlinucb_head's losses under the reference's LOSS_TYPES names
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
@@ -337,6 +339,13 @@ SIGNATURES = {
                                         c_void_p, c_void_p]),
     "rg_sched_tick": (c_int, [c_void_p, c_void_p]),
     "rg_sched_tick_many": (c_int, [ctypes.POINTER(c_void_p), c_int, c_void_p]),
+    "rg_lstm_forward": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3 + [c_void_p]),
+    "rg_lstm_backward": (c_int, [c_void_p] * 5 + [c_int] * 3 + [c_void_p] * 3 + [c_void_p]),
+    "rg_mdn_head_partials": (c_int, [c_int]),
+    "rg_mdn_head": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_d, c_d, c_d] + [c_int] * 5
+                    + [c_void_p, c_i64] + [c_void_p] * 4 + [c_void_p]),
+    "rg_mdn_outputs": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rg_mdn_gmm_nll": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p]),
 }
 
 _lib = None

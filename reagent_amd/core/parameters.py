@@ -1,5 +1,5 @@
 """Parameter dataclasses with the field names / defaults of reagent/core/parameters.py
-(SlateOptParameters :33-43, RLParameters :46-67, EvaluationParameters :118-120, NormalizationParameters :138-152).
+(SlateOptParameters :33-43, RLParameters :46-67, MDNRNNTrainerParameters :70-85, EvaluationParameters :118-120, NormalizationParameters :138-152).
 Objects of the reference's own classes are accepted anywhere these are (duck typing)."""
 import enum
 from dataclasses import dataclass, field
@@ -37,6 +37,22 @@ class RLParameters:
     time_diff_unit_length: float = 1.0
     multi_steps: Optional[int] = None
     ratio_different_predictions_tolerance: float = 0
+
+
+@dataclass(frozen=True)
+class MDNRNNTrainerParameters:
+    hidden_size: int = 64
+    num_hidden_layers: int = 2
+    learning_rate: float = 0.001
+    num_gaussians: int = 5
+    # weight in calculating world-model loss
+    reward_loss_weight: float = 1.0
+    next_state_loss_weight: float = 1.0
+    not_terminal_loss_weight: float = 1.0
+    fit_only_one_next_step: bool = False
+    action_dim: int = 2
+    action_names: Optional[List[str]] = None
+    multi_steps: int = 1
 
 
 @dataclass(frozen=True)

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -13,7 +13,8 @@ by class OBJECT — `make_trainer_preprocessor` reads the annotation of `train_s
 `REAGENT_AMD_OWN_TYPES=1` keeps the restatements.
 """
 import dataclasses
-from dataclasses import dataclass
+import logging
+from dataclasses import dataclass, field
 from typing import Optional
 
 import torch
@@ -96,6 +97,11 @@ class DocList(TensorDataClass):
         return FeatureData(self.float_features.view(-1, feature_dim))
 
 
+_FLOAT_FEATURES_USAGE = ("For sequence features, use `stacked_float_features`."
+                         "For document features, use `candidate_doc_float_features`.")
+_warned_3d = False  # the reference's no_dup_logger: the message once per process
+
+
 @dataclass
 class FeatureData(TensorDataClass):
     float_features: torch.Tensor
@@ -107,9 +113,17 @@ class FeatureData(TensorDataClass):
     time_since_first: Optional[torch.Tensor] = None
 
     def __post_init__(self):
+        # run_post_init_validation (:294-309): 3-D (the world model's [seq_len, batch, dim]) passes with one warning
         ff = self.float_features
-        if isinstance(ff, torch.Tensor) and ff.ndim != 2:
-            raise ValueError(f"float_features should be 2D; got {ff.shape}.")
+        if not isinstance(ff, torch.Tensor) or ff.ndim == 2:
+            return
+        if ff.ndim == 3:
+            global _warned_3d
+            if not _warned_3d:
+                _warned_3d = True
+                logging.getLogger(__name__).warning(f"`float_features` should be 2D.\n{_FLOAT_FEATURES_USAGE}")
+            return
+        raise ValueError(f"float_features should be 2D; got {ff.shape}.")
 
     def get_tiled_batch(self, num_tiles: int):
         """:349-364 — tiled[i * num_tiles:(i + 1) * num_tiles] == float_features[i].  A utility entry point: the
@@ -385,6 +399,50 @@ class CBInput(TensorDataClass):
         return weight
 
 
+@dataclass
+class MemoryNetworkInput(BaseInput):
+    """:1017-1046 — the world model's batch: every tensor sequence first, [seq_len, batch, ...]"""
+
+    action: FeatureData
+    valid_step: Optional[torch.Tensor] = None  # carried, unused (as in the reference's trainer)
+    extras: ExtraData = field(default_factory=ExtraData)
+
+    @classmethod
+    def from_dict(cls, d):
+        return cls(
+            state=FeatureData(float_features=d["state"]),
+            next_state=FeatureData(float_features=d["next_state"]),
+            action=FeatureData(float_features=d["action"]),
+            reward=d["reward"],
+            time_diff=d["time_diff"],
+            not_terminal=d["not_terminal"],
+            step=d["step"],
+            extras=ExtraData.from_dict(d),
+        )
+
+    def __len__(self):
+        n = self.state.float_features.ndim
+        if n == 2:
+            return self.state.float_features.size()[0]
+        if n == 3:
+            return self.state.float_features.size()[1]
+        raise NotImplementedError()
+
+
+@dataclass
+class MemoryNetworkOutput(TensorDataClass):
+    """:1057-1066"""
+
+    mus: torch.Tensor
+    sigmas: torch.Tensor
+    logpi: torch.Tensor
+    reward: torch.Tensor
+    not_terminal: torch.Tensor
+    last_step_lstm_hidden: torch.Tensor
+    last_step_lstm_cell: torch.Tensor
+    all_steps_lstm_hidden: torch.Tensor
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -406,7 +464,8 @@ USING_REFERENCE_TYPES = False
 _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
-                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput"):
+                  "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput", "MemoryNetworkInput",
+                  "MemoryNetworkOutput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

@@ -1,0 +1,300 @@
+// lstm.hip — one nn.LSTM layer over a whole sequence, forward and backward (the world model's recurrence, reagent/models/
+// mdn_rnn.py:32-36, 72).  The recurrence couples hidden units but never batch rows, so a workgroup owns a tile of 32 batch
+// rows for all T steps: one launch per layer and direction, no cooperative launch, no flag a workgroup waits on, no
+// atomics.  The tile's h_{t-1} (forward), or d loss / d h and d loss / d c carried back from step t + 1 (backward), live in
+// LDS; the four waves split the hidden units in tiles of 32 and a wave holds the i, f, g, o accumulators of the same 32
+// units, so the cell update needs no exchange.  Products run on v_mfma_f32_32x32x2_f32 (exact fp32 products, fp32
+// accumulation in k order); the gate arithmetic (sigmoid, tanh, the cell update and their derivatives) runs in double on the
+// fp32 accumulators and is rounded once where it is stored.  Trip counts depend on H alone, a row's bits on that row alone.
+#include <rg_platform.h>
+#include "../../include/reagent_hip.h"
+
+namespace rg {
+
+constexpr int LSTM_THREADS = 256;
+constexpr int LSTM_WAVES = LSTM_THREADS / 64;
+constexpr int LSTM_ROWS = 32;  // batch rows per workgroup: one MFMA tile of rows
+constexpr int LSTM_TILE = 32;  // hidden units per accumulator tile
+
+// exp in double with its constants read from LDS.  The library's exp keeps sixteen 64-bit constants, which the compiler hoists
+// out of the step loop into scalar registers for the whole kernel: with the kernel's own scalars that is more than a wave has,
+// and it spills them.  Read from LDS inside the loop they are vector registers for the length of a tile's epilogue only.
+// exp(x) = 2^k * exp(r), k = rint(x / ln 2), r = x - k * ln2_hi - k * ln2_lo (|r| <= 0.347), exp(r) by its series to r^13
+// (the next term is under 4e-18).  The argument is clamped to where the result is a finite double.
+constexpr int LSTM_EXP_COEFS = 15;
+__device__ __forceinline__ void lstm_exp_table(double* c) {  // by one thread, before the workgroup's first barrier
+  c[0] = 1.44269504088896338700e+00;  // 1 / ln 2
+  c[1] = 6.93147180369123816490e-01;  // ln2_hi: the low 32 bits of the fraction are zero, so k * ln2_hi is exact
+  c[2] = 1.90821492927058770002e-10;  // ln2_lo
+  double f = 1.0;
+  for (int n = 2; n <= 13; ++n) {
+    f *= (double)n;
+    c[16 - n] = 1.0 / f;  // c[3] = 1 / 13!, ..., c[14] = 1 / 2!
+  }
+}
+__device__ __forceinline__ double lstm_exp(double x, const double* c) {
+  x = fmin(fmax(x, -745.0), 709.0);
+  const double k = rint(x * c[0]);
+  const double r = fma(-k, c[2], fma(-k, c[1], x));
+  double p = c[3];
+#pragma unroll
+  for (int i = 4; i < LSTM_EXP_COEFS; ++i) p = fma(p, r, c[i]);
+  return ldexp(fma(p, r * r, r) + 1.0, (int)k);
+}
+__device__ __forceinline__ double lstm_sigmoid(double x, const double* c) { return 1.0 / (1.0 + lstm_exp(-x, c)); }
+// tanh through the same exponential: (1 - e) / (1 + e) with e = exp(-2 |x|), relative error below 2e-14 from |x| = 2^-8 up;
+// below it the odd series to x^7, whose next term is under 1e-21 x
+__device__ __forceinline__ double lstm_tanh(double x, const double* c) {
+  const double ax = fabs(x), x2 = x * x;
+  const double e = lstm_exp(-2.0 * ax, c);
+  const double big = copysign((1.0 - e) / (1.0 + e), x);
+  const double small = x * (1.0 - x2 * (1.0 / 3.0 - x2 * (2.0 / 15.0 - x2 * (17.0 / 315.0))));
+  return ax < 0x1p-8 ? small : big;
+}
+// row of accumulator register r in the 32x32 result tile (column = lane & 31)
+__device__ __forceinline__ int lstm_acc_row(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
+
+// registers 4q .. 4q + 3 of an accumulator (rows 8q + 4 * half + 0 .. 3) for a wave-uniform q: selects, not an indexed
+// register file
+__device__ __forceinline__ f32x4 lstm_acc_quad(const f32x16& v, int q) {
+  f32x4 o;
+  switch (q) {
+    case 0: o[0] = v[0], o[1] = v[1], o[2] = v[2], o[3] = v[3]; break;
+    case 1: o[0] = v[4], o[1] = v[5], o[2] = v[6], o[3] = v[7]; break;
+    case 2: o[0] = v[8], o[1] = v[9], o[2] = v[10], o[3] = v[11]; break;
+    default: o[0] = v[12], o[1] = v[13], o[2] = v[14], o[3] = v[15]; break;
+  }
+  return o;
+}
+
+static int lstm_padded(int H) { return (H + LSTM_TILE - 1) / LSTM_TILE * LSTM_TILE; }
+static size_t lstm_tile_floats(int H) { return (size_t)LSTM_ROWS * (lstm_padded(H) + 1); }
+
+struct LstmFwdArgs {
+  const float *xproj, *w_hh, *b_hh, *h0, *c0;
+  float *h_all, *c_all, *gates;
+  int T, B, H, Hp;
+};
+
+// Step t of a row tile: pre = xproj[t] + b_hh + h_{t-1} * W_hh^T, (i, f, o) = sigmoid, g = tanh, c_t = f * c_{t-1} + i * g,
+// h_t = o * tanh(c_t).  h_{t-1} is read from one LDS image (pitch Hp + 1: the A fragment's 32 rows fall on 32 banks) while
+// h_t is written to the other; units and rows past the end hold zeros there, so the K loop runs over Hp for every tile.
+// c_{t-1} is what this same thread stored to c_all one step earlier (its own store: no fence needed).
+__global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) lstm_forward_kernel(const LstmFwdArgs a) {
+  RG_DYN_LDS(smem);
+  __shared__ double ec[LSTM_EXP_COEFS];
+  if (threadIdx.x == 0) lstm_exp_table(ec);
+  const int H = a.H, Hp = a.Hp, B = a.B, pitch = Hp + 1, tiles = Hp / LSTM_TILE;
+  float* cur = (float*)smem;
+  float* nxt = cur + LSTM_ROWS * pitch;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
+  const long row0 = (long)blockIdx.x * LSTM_ROWS;
+  for (int e = threadIdx.x; e < LSTM_ROWS * Hp; e += LSTM_THREADS) {
+    const int r = e / Hp, u = e % Hp;
+    const long row = row0 + r;
+    cur[r * pitch + u] = (a.h0 && row < B && u < H) ? a.h0[row * H + u] : 0.f;
+  }
+  __syncthreads();
+  for (int t = 0; t < a.T; ++t) {
+    for (int tile = wave; tile < tiles; tile += LSTM_WAVES) {
+      const int u = tile * LSTM_TILE + col;
+      const bool u_ok = u < H;
+      const int uc = u_ok ? u : H - 1;
+      const float* wi = a.w_hh + (long)uc * H;
+      const float* wf = wi + (long)H * H;
+      const float* wg = wf + (long)H * H;
+      const float* wo = wg + (long)H * H;
+      f32x16 ai, af, ag, ao;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) ai[r] = 0.f, af[r] = 0.f, ag[r] = 0.f, ao[r] = 0.f;
+#pragma unroll 4
+      for (int k = 0; k < Hp; k += 2) {
+        const int kk = k + half;  // (< Hp: Hp is even)
+        const bool ok = u_ok && kk < H;
+        const int kc = kk < H ? kk : 0;
+        const float av = cur[col * pitch + kk];
+        const float bi = wi[kc], bf = wf[kc], bg = wg[kc], bo = wo[kc];
+        ai = mfma_32x32x2_f32(av, ok ? bi : 0.f, ai);
+        af = mfma_32x32x2_f32(av, ok ? bf : 0.f, af);
+        ag = mfma_32x32x2_f32(av, ok ? bg : 0.f, ag);
+        ao = mfma_32x32x2_f32(av, ok ? bo : 0.f, ao);
+      }
+      double bias[4];
+#pragma unroll
+      for (int g = 0; g < 4; ++g) bias[g] = a.b_hh ? (double)a.b_hh[g * H + uc] : 0.0;
+#pragma unroll 1
+      for (int q = 0; q < 4; ++q) {  // four rows at a time: the double arithmetic below is compiled once, not sixteen times
+        const f32x4 qi = lstm_acc_quad(ai, q), qf = lstm_acc_quad(af, q), qg = lstm_acc_quad(ag, q), qo = lstm_acc_quad(ao, q);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int rl = lstm_acc_row(4 * q + j, half);
+          const long row = row0 + rl;
+          const bool ok = u_ok && row < B;
+          const long rowc = row < B ? row : B - 1;  // (addresses stay inside the arrays; the values are dropped)
+          const long at = ((long)t * B + rowc) * H + uc;
+          const float* xp = a.xproj + ((long)t * B + rowc) * 4 * H + uc;
+          const double gi = lstm_sigmoid((double)qi[j] + (double)xp[0] + bias[0], ec);
+          const double gf = lstm_sigmoid((double)qf[j] + (double)xp[H] + bias[1], ec);
+          const double gg = lstm_tanh((double)qg[j] + (double)xp[2 * H] + bias[2], ec);
+          const double go = lstm_sigmoid((double)qo[j] + (double)xp[3 * H] + bias[3], ec);
+          const float cp = t == 0 ? (a.c0 ? a.c0[rowc * H + uc] : 0.f) : a.c_all[at - (long)B * H];
+          const float c = (float)(gf * (double)cp + gi * gg);
+          const float h = (float)(go * lstm_tanh((double)c, ec));  // of the stored c: the backward takes tanh of the same value
+          if (ok) {
+            a.h_all[at] = h;
+            a.c_all[at] = c;
+            if (a.gates) {
+              float* gp = a.gates + ((long)t * B + row) * 4 * H + u;
+              gp[0] = (float)gi, gp[H] = (float)gf, gp[2 * H] = (float)gg, gp[3 * H] = (float)go;
+            }
+          }
+          nxt[rl * pitch + u] = ok ? h : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    float* s = cur;
+    cur = nxt, nxt = s;
+  }
+}
+
+struct LstmBwdArgs {
+  const float *dh_all, *gates, *c_all, *c0, *w_hh;
+  float *dgates, *dh0, *dc0;
+  int T, B, H, Hp;
+};
+
+// Step t of a row tile, from the last step down.  Per element: dh = dh_all[t] + dh_rec, d_o = dh * tanh(c_t), dc = dc_next +
+// dh * o * (1 - tanh(c_t)^2), d_i = dc * g, d_f = dc * c_{t-1}, d_g = dc * i, dc_next = dc * f, each times its gate's
+// derivative: dgates[t] = d loss / d pre-activation.  Then dh_rec = dgates[t] * W_hh (K = 4H): the operand tile is 32 x 4H
+// fp32, 128 KB at H = 256, so it is staged one gate (32 x H) at a time from the dgates rows the workgroup has just written
+// (its own stores, after a barrier).  W_hh is read in place: lane n of the B fragment reads row k's element n (coalesced).
+__global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) lstm_backward_kernel(const LstmBwdArgs a) {
+  RG_DYN_LDS(smem);
+  __shared__ double ec[LSTM_EXP_COEFS];
+  if (threadIdx.x == 0) lstm_exp_table(ec);
+  const int H = a.H, Hp = a.Hp, B = a.B, pitch = Hp + 1, tiles = Hp / LSTM_TILE;
+  float* dhrec = (float*)smem;
+  float* dc = dhrec + LSTM_ROWS * pitch;
+  float* stage = dc + LSTM_ROWS * pitch;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, col = lane & 31, half = lane >> 5;
+  const long row0 = (long)blockIdx.x * LSTM_ROWS;
+  for (int e = threadIdx.x; e < LSTM_ROWS * pitch; e += LSTM_THREADS) dhrec[e] = 0.f, dc[e] = 0.f;
+  __syncthreads();
+  for (int t = a.T - 1; t >= 0; --t) {
+    for (int e = threadIdx.x; e < LSTM_ROWS * Hp; e += LSTM_THREADS) {
+      const int r = e / Hp, u = e % Hp;
+      const long row = row0 + r;
+      if (row < B && u < H) {
+        const long at = ((long)t * B + row) * H + u;
+        const long gat = ((long)t * B + row) * 4 * H + u;
+        const double gi = a.gates[gat], gf = a.gates[gat + H], gg = a.gates[gat + 2 * H], go = a.gates[gat + 3 * H];
+        const double cp = t == 0 ? (a.c0 ? (double)a.c0[row * H + u] : 0.0) : (double)a.c_all[at - (long)B * H];
+        const double tc = lstm_tanh((double)a.c_all[at], ec);
+        const double dh = (double)a.dh_all[at] + (double)dhrec[r * pitch + u];
+        const double dct = (double)dc[r * pitch + u] + dh * go * (1.0 - tc * tc);
+        dc[r * pitch + u] = (float)(dct * gf);
+        a.dgates[gat] = (float)(dct * gg * gi * (1.0 - gi));
+        a.dgates[gat + H] = (float)(dct * cp * gf * (1.0 - gf));
+        a.dgates[gat + 2 * H] = (float)(dct * gi * (1.0 - gg * gg));
+        a.dgates[gat + 3 * H] = (float)(dh * tc * go * (1.0 - go));
+      }
+    }
+    __syncthreads();
+    f32x16 acc[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[q][r] = 0.f;
+    for (int gate = 0; gate < 4; ++gate) {
+      for (int e = threadIdx.x; e < LSTM_ROWS * Hp; e += LSTM_THREADS) {
+        const int r = e / Hp, u = e % Hp;
+        const long row = row0 + r;
+        stage[r * pitch + u] = (row < B && u < H) ? a.dgates[((long)t * B + row) * 4 * H + gate * H + u] : 0.f;
+      }
+      __syncthreads();
+      const float* w = a.w_hh + (long)gate * H * H;
+#pragma unroll
+      for (int q = 0; q < 2; ++q) {
+        const int tile = wave + q * LSTM_WAVES;
+        if (tile < tiles) {  // (wave-uniform; at most 2 * LSTM_WAVES tiles: H <= RG_LSTM_MAX_HIDDEN)
+          const int n = tile * LSTM_TILE + col;
+          const bool n_ok = n < H;
+          const int nc = n_ok ? n : H - 1;
+#pragma unroll 4
+          for (int k = 0; k < Hp; k += 2) {
+            const int kk = k + half;
+            const bool ok = n_ok && kk < H;
+            const float bv = w[(long)(kk < H ? kk : 0) * H + nc];
+            acc[q] = mfma_32x32x2_f32(stage[col * pitch + kk], ok ? bv : 0.f, acc[q]);
+          }
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int tile = wave + q * LSTM_WAVES;
+      if (tile < tiles) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) dhrec[lstm_acc_row(r, half) * pitch + tile * LSTM_TILE + col] = acc[q][r];
+      }
+    }
+    __syncthreads();
+  }
+  for (int e = threadIdx.x; e < LSTM_ROWS * Hp; e += LSTM_THREADS) {
+    const int r = e / Hp, u = e % Hp;
+    const long row = row0 + r;
+    if (row < B && u < H) {
+      if (a.dh0) a.dh0[row * H + u] = dhrec[r * pitch + u];
+      if (a.dc0) a.dc0[row * H + u] = dc[r * pitch + u];
+    }
+  }
+}
+
+static int lstm_check(int seq_len, int batch, int hidden) {
+  if (seq_len < 1 || batch < 1 || hidden < 1) return RG_EINVAL;
+  if (hidden > RG_LSTM_MAX_HIDDEN) return RG_EUNSUPPORTED;
+  if ((int64_t)seq_len * batch > 0x7fffffffLL / 4) return RG_EUNSUPPORTED;  // T * B rows go through rg_fc_* as an int
+  return RG_OK;
+}
+
+}  // namespace rg
+
+using namespace rg;
+
+extern "C" {
+
+int rg_lstm_forward(const float* xproj, const float* w_hh, const float* b_hh, const float* h0, const float* c0, int seq_len,
+                    int batch, int hidden, float* h_all, float* c_all, float* gates, rg_stream_t stream) {
+  const int rc = lstm_check(seq_len, batch, hidden);
+  if (rc != RG_OK) return rc;
+  if (!xproj || !w_hh || !h_all || !c_all) return RG_EINVAL;
+  LstmFwdArgs a;
+  a.xproj = xproj, a.w_hh = w_hh, a.b_hh = b_hh, a.h0 = h0, a.c0 = c0;
+  a.h_all = h_all, a.c_all = c_all, a.gates = gates;
+  a.T = seq_len, a.B = batch, a.H = hidden, a.Hp = lstm_padded(hidden);
+  const size_t lds = 2 * lstm_tile_floats(hidden) * sizeof(float);
+  RG_ALLOW_LDS(lstm_forward_kernel, lds);
+  RG_LAUNCH_DYN(lstm_forward_kernel, dim3((batch + LSTM_ROWS - 1) / LSTM_ROWS), dim3(LSTM_THREADS), lds,
+                (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+int rg_lstm_backward(const float* dh_all, const float* gates, const float* c_all, const float* c0, const float* w_hh,
+                     int seq_len, int batch, int hidden, float* dgates, float* dh0, float* dc0, rg_stream_t stream) {
+  const int rc = lstm_check(seq_len, batch, hidden);
+  if (rc != RG_OK) return rc;
+  if (!dh_all || !gates || !c_all || !w_hh || !dgates) return RG_EINVAL;
+  LstmBwdArgs a;
+  a.dh_all = dh_all, a.gates = gates, a.c_all = c_all, a.c0 = c0, a.w_hh = w_hh;
+  a.dgates = dgates, a.dh0 = dh0, a.dc0 = dc0;
+  a.T = seq_len, a.B = batch, a.H = hidden, a.Hp = lstm_padded(hidden);
+  const size_t lds = 3 * lstm_tile_floats(hidden) * sizeof(float);
+  RG_ALLOW_LDS(lstm_backward_kernel, lds);
+  RG_LAUNCH_DYN(lstm_backward_kernel, dim3((batch + LSTM_ROWS - 1) / LSTM_ROWS), dim3(LSTM_THREADS), lds,
+                (hipStream_t)stream, a);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

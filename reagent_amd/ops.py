@@ -663,6 +663,101 @@ def pg_head(scores, action, returns, values, old_log_prob, temperature, mode: in
                                     L.ptr(policy_partials), L.ptr(value_partials), L.stream_ptr()))
 
 
+# ---- world model (MDN-RNN) --------------------------------------------------------------------------------------
+def _lstm_check(T, B, H):
+    if H > L.LSTM_MAX_HIDDEN:
+        raise NotImplementedError(f"LSTM kernels: hidden size {H} is not supported (1 .. {L.LSTM_MAX_HIDDEN})")
+    if T * B >= 1 << 29:
+        raise NotImplementedError(f"LSTM kernels: seq_len * batch = {T * B} is not supported (below 2^29)")
+    assert T >= 1 and B >= 1 and H >= 1
+
+
+def _f32_flat(t, numel):
+    assert t is None or (t.dtype == F32 and t.is_contiguous() and t.numel() == numel), "expected a contiguous fp32 tensor"
+
+
+def lstm_forward(xproj, w_hh, b_hh, h0, c0, h_all, c_all, gates=None):
+    """one LSTM layer over the whole sequence (see rg_lstm_forward): xproj [T, B, 4H] = x @ W_ih.T + b_ih, w_hh [4H, H];
+    b_hh, h0, c0 may be None (zeros); gates=None saves nothing for a backward"""
+    _chk_dev(xproj, w_hh, b_hh, h0, c0, h_all, c_all, gates)
+    T, B, H4 = xproj.shape
+    H = H4 // 4
+    _lstm_check(T, B, H)
+    assert H4 == 4 * H and w_hh.shape == (4 * H, H)
+    _f32_flat(xproj, T * B * 4 * H), _f32_flat(w_hh, 4 * H * H), _f32_flat(b_hh, 4 * H), _f32_flat(gates, T * B * 4 * H)
+    _f32_flat(h0, B * H), _f32_flat(c0, B * H), _f32_flat(h_all, T * B * H), _f32_flat(c_all, T * B * H)
+    _run("rg_lstm_forward", dict(T=T, B=B, H=H, save=gates is not None),
+         lambda: L.lib().rg_lstm_forward(L.ptr(xproj), L.ptr(w_hh), L.ptr(b_hh), L.ptr(h0), L.ptr(c0), T, B, H, L.ptr(h_all),
+                                         L.ptr(c_all), L.ptr(gates), L.stream_ptr()))
+
+
+def lstm_backward(dh_all, gates, c_all, c0, w_hh, dgates, dh0=None, dc0=None):
+    """the layer's backward (see rg_lstm_backward): dgates [T, B, 4H] = d loss / d pre-activation, dh0 / dc0 [B, H]"""
+    _chk_dev(dh_all, gates, c_all, c0, w_hh, dgates, dh0, dc0)
+    T, B, H = dh_all.shape
+    _lstm_check(T, B, H)
+    assert w_hh.shape == (4 * H, H)
+    _f32_flat(dh_all, T * B * H), _f32_flat(c_all, T * B * H), _f32_flat(gates, T * B * 4 * H), _f32_flat(dgates, T * B * 4 * H)
+    _f32_flat(w_hh, 4 * H * H), _f32_flat(c0, B * H), _f32_flat(dh0, B * H), _f32_flat(dc0, B * H)
+    _run("rg_lstm_backward", dict(T=T, B=B, H=H),
+         lambda: L.lib().rg_lstm_backward(L.ptr(dh_all), L.ptr(gates), L.ptr(c_all), L.ptr(c0), L.ptr(w_hh), T, B, H,
+                                          L.ptr(dgates), L.ptr(dh0), L.ptr(dc0), L.stream_ptr()))
+
+
+def _mdn_check(G, S):
+    if G > L.MDN_MAX_GAUSSIANS:
+        raise NotImplementedError(f"mixture-density head: {G} gaussians are not supported (1 .. {L.MDN_MAX_GAUSSIANS})")
+    if S > L.MDN_MAX_STATE_DIM:
+        raise NotImplementedError(f"mixture-density head: state_dim {S} is not supported (1 .. {L.MDN_MAX_STATE_DIM})")
+    assert G >= 1 and S >= 1
+
+
+def mdn_head_partials(n: int) -> int:
+    return int(L.lib().rg_mdn_head_partials(n))
+
+
+def mdn_head(z, next_state, reward, not_terminal, num_gaussians: int, weights, divide_by_state_dim: bool, first_row: int, dz,
+             partials, losses, sigmas=None, logpi=None):
+    """the mixture-density head over z [N, (2S + 1) G + 2] (see rg_mdn_head): weights = (next_state, not_terminal, reward)
+    loss weights; losses [4] = gmm, bce, mse, loss; partials: float64 [3 * mdn_head_partials(N)]"""
+    _chk_dev(z, next_state, reward, not_terminal, dz, partials, losses, sigmas, logpi)
+    N, S = next_state.shape
+    G = int(num_gaussians)
+    _mdn_check(G, S)
+    width = (2 * S + 1) * G + 2
+    assert z.dtype == dz.dtype == F32 and z.shape == (N, width) == dz.shape and 0 <= first_row < N
+    _f32_flat(next_state, N * S), _f32_flat(reward, N), _f32_flat(not_terminal, N), _f32_flat(losses, 4)
+    _f32_flat(sigmas, N * G * S), _f32_flat(logpi, N * G)
+    assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= 3 * mdn_head_partials(N)
+    w = [float(x) for x in weights]
+    _run("rg_mdn_head", dict(N=N, G=G, S=S),
+         lambda: L.lib().rg_mdn_head(L.ptr(z), _ld(z), L.ptr(next_state), L.ptr(reward), L.ptr(not_terminal), w[0], w[1], w[2],
+                                     int(bool(divide_by_state_dim)), int(first_row), N, G, S, L.ptr(dz), _ld(dz),
+                                     L.ptr(sigmas), L.ptr(logpi), L.ptr(partials), L.ptr(losses), L.stream_ptr()))
+
+
+def mdn_outputs(z, num_gaussians: int, state_dim: int, sigmas, logpi):
+    """sigmas [N, G, S] = exp(z's log sigmas), logpi [N, G] = log_softmax(z's mixture logits) (see rg_mdn_outputs)"""
+    _chk_dev(z, sigmas, logpi)
+    N, G, S = z.shape[0], int(num_gaussians), int(state_dim)
+    _mdn_check(G, S)
+    assert z.dtype == F32 and z.shape == (N, (2 * S + 1) * G + 2)
+    _f32_flat(sigmas, N * G * S), _f32_flat(logpi, N * G)
+    _run("rg_mdn_outputs", dict(N=N, G=G, S=S),
+         lambda: L.lib().rg_mdn_outputs(L.ptr(z), _ld(z), N, G, S, L.ptr(sigmas), L.ptr(logpi), L.stream_ptr()))
+
+
+def mdn_gmm_nll(batch, mus, sigmas, logpi, nll):
+    """nll [N] = gmm_loss(batch [N, S], mus [N, G, S], sigmas [N, G, S], logpi [N, G], reduce=False)"""
+    _chk_dev(batch, mus, sigmas, logpi, nll)
+    N, G, S = mus.shape
+    _mdn_check(G, S)
+    _f32_flat(batch, N * S), _f32_flat(mus, N * G * S), _f32_flat(sigmas, N * G * S), _f32_flat(logpi, N * G), _f32_flat(nll, N)
+    _run("rg_mdn_gmm_nll", dict(N=N, G=G, S=S),
+         lambda: L.lib().rg_mdn_gmm_nll(L.ptr(batch), L.ptr(mus), L.ptr(sigmas), L.ptr(logpi), N, G, S, L.ptr(nll),
+                                        L.stream_ptr()))
+
+
 def linucb_workspace(batch: int, dim: int, device) -> torch.Tensor:
     """the byte workspace rg_linucb_accumulate asks for at (batch, dim)"""
     n = int(L.lib().rg_linucb_workspace_bytes(int(batch), int(dim)))

@@ -182,6 +182,31 @@ def to_pg_input(d: Dict[str, torch.Tensor], device=None):
     return rlt.PolicyGradientInput.from_dict({k: (v.to(device) if device is not None else v) for k, v in d.items()})
 
 
+def memory_network_batch(seq_len: int, batch: int, state_dim: int, action_dim: int, seed: int = 0,
+                         p_terminal: float = 0.2) -> Dict[str, torch.Tensor]:
+    """The keys rlt.MemoryNetworkInput.from_dict reads, sequence first: state / next_state [T, B, S] ~ N(0, 1) (next_state =
+    a noisy linear mix of state and action, so there is something to learn), action [T, B, A] ~ N(0, 1), reward [T, B] ~
+    N(0, 1), not_terminal [T, B] in {0, 1} mixed, time_diff ones, step None"""
+    g = torch.Generator().manual_seed(seed)
+    T, B, S, A = seq_len, batch, state_dim, action_dim
+    state = torch.randn(T, B, S, generator=g)
+    action = torch.randn(T, B, A, generator=g)
+    mix_s = torch.randn(S, S, generator=g) / S ** 0.5
+    mix_a = torch.randn(A, S, generator=g) / A ** 0.5
+    next_state = state @ mix_s + action @ mix_a + 0.1 * torch.randn(T, B, S, generator=g)
+    reward = torch.randn(T, B, generator=g)
+    not_terminal = (torch.rand(T, B, generator=g) > p_terminal).float()
+    return dict(state=state, action=action, next_state=next_state, reward=reward, not_terminal=not_terminal,
+                time_diff=torch.ones(T, B), step=None)
+
+
+def to_memory_network_input(d: Dict[str, torch.Tensor], device=None):
+    from .core import types as rlt
+
+    return rlt.MemoryNetworkInput.from_dict({k: (v.to(device) if device is not None and v is not None else v)
+                                             for k, v in d.items()})
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 
