@@ -1308,6 +1308,58 @@ int rg_mdn_outputs(const float* z, int64_t ldz, int n, int num_gaussians, int st
 int rg_mdn_gmm_nll(const float* batch, const float* mus, const float* sigmas, const float* logpi, int n, int num_gaussians,
                    int state_dim, float* nll, rg_stream_t stream);
 
+/* World model: Seq2Reward (reagent/models/seq2reward_model.py, reagent/training/world_model/seq2reward_trainer.py,
+ * compress_model_trainer.py).  Additive symbols: the ABI number does not move.  All fp32, every array contiguous.
+ *
+ * rg_lstm_fanout_step: one LSTM layer, ONE time step, over n = parents * fanout child rows of a prefix tree: the planning
+ * step get_Q (seq2reward_trainer.py:31-64) without the enumeration's repeated prefixes.  Child r takes h_prev and c_prev
+ * [parents, H] (c_prev NULL: zeros) from row r / fanout, and its input projection x * W_ih^T + b_ih from row r % table_rows
+ * of proj [table_rows, 4H] when table_rows > 0 (layer 0: the projection of a one-hot action is a row of the projected
+ * identity, and with table_rows = fanout = A child r's action is r % A), or from row r of proj [n, 4H] when table_rows = 0
+ * (upper layers: rg_fc_forward on the layer below's child h).  Writes h, c [n, H].  The tile shape and arithmetic are
+ * rg_lstm_forward's (32 rows per workgroup, the k-ordered v_mfma_f32_32x32x2_f32 chain over H, gates in double, rounded
+ * once): a child's bits are those of rg_lstm_forward with seq_len = 1 on the materialised h0 / c0 / xproj rows.
+ * RG_EINVAL for parents, fanout or hidden < 1, table_rows < 0 or a null pointer other than c_prev and b_hh;
+ * RG_EUNSUPPORTED for hidden > RG_LSTM_MAX_HIDDEN or n >= 2^29.
+ *
+ * rg_seq2reward_plan_max: acc[r] = h[r] . w + bias[0] over the leaf rows h [groups * group_size, H] (lstm_linear,
+ * seq2reward_model.py:63: accumulated in double in index order, rounded once), q[g] = the max over group g's group_size
+ * consecutive leaves (seq2reward_trainer.py:60-62 with groups = B * A and group_size = P / A: the leaves of one first
+ * action).  A NaN among a group's leaves gives NaN, as torch.max does.  One wave per group, any group_size.
+ * RG_EINVAL for groups, group_size or hidden < 1 or a null pointer; RG_EUNSUPPORTED for groups * group_size >= 2^29.
+ *
+ * rg_seq2reward_head: the training head over B rows (seq2reward_model.py:62-68, seq2reward_trainer.py:216-245).  h_all
+ * [T, B, H] = the top layer's hidden states; valid_step [B] int64, CLAMPED into [1, T] inside the kernel (the reference
+ * indexes with it as it is and faults outside that range); reward [T, B]; gamma_pow [T] = fp32(gamma ** i).
+ *   pred[b] = h_all[v - 1, b] . w + bias[0]                              (double in index order, rounded once: acc_reward [B])
+ *   target[b] = sum_{i < v} reward[i, b] * gamma_pow[i]                  (an fp32 product, then a sequential fp32 sum)
+ *   loss = mean_b (pred - target)^2
+ * Outputs: acc_reward [B]; dh_all [T, B, H] = d loss / d h_all, written entirely (zero except at step v - 1 of each row);
+ * dw [H], dbias [1], loss [1] from per-workgroup double partials (partials: (H + 2) * rg_seq2reward_head_partials(B)
+ * doubles) added in a fixed order by a finishing launch.  With valid_step NULL: the last step of every row.  With dh_all
+ * NULL: acc_reward alone, the forward of Seq2RewardNetwork (reward, gamma_pow, dw, dbias, partials and loss are not read or
+ * written and may be NULL).
+ * RG_EINVAL for seq_len, batch or hidden < 1 or a null pointer the mode needs; RG_EUNSUPPORTED for seq_len * batch >= 2^29.
+ *
+ * rg_step_ce_head: nn.CrossEntropyLoss(mean) of logits [B, K] against valid_step - 1 (seq2reward_trainer.py:261-267), the
+ * step clamped into [1, K]: loss [1], dlogits [B, K] = (softmax - onehot) / B, and (nullable) softmax [B, K]
+ * (get_step_prediction, :21-27).  With valid_step NULL: the softmax alone.  A 32-lane group per row, in double, rounded once;
+ * partials: rg_step_ce_head_partials(B) doubles, added in a fixed order by a finishing launch.
+ * RG_EINVAL for batch or classes < 1 or a null pointer the mode needs; RG_EUNSUPPORTED for classes > RG_STEP_CE_MAX_CLASSES.
+ * No atomics anywhere: two runs give the same bits. */
+#define RG_STEP_CE_MAX_CLASSES 32
+int rg_lstm_fanout_step(const float* h_prev, const float* c_prev, const float* proj, int table_rows, const float* w_hh,
+                        const float* b_hh, int parents, int fanout, int hidden, float* h, float* c, rg_stream_t stream);
+int rg_seq2reward_plan_max(const float* h, const float* w, const float* bias, int groups, int group_size, int hidden, float* q,
+                           rg_stream_t stream);
+int rg_seq2reward_head_partials(int batch);
+int rg_seq2reward_head(const float* h_all, const int64_t* valid_step, const float* reward, const float* gamma_pow,
+                       const float* w, const float* bias, int seq_len, int batch, int hidden, float* acc_reward, float* dh_all,
+                       float* dw, float* dbias, double* partials, float* loss, rg_stream_t stream);
+int rg_step_ce_head_partials(int batch);
+int rg_step_ce_head(const float* logits, const int64_t* valid_step, int batch, int classes, float* dlogits, float* softmax,
+                    double* partials, float* loss, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,7 @@ LINUCB_MAX_DIM = 512  # RG_LINUCB_MAX_DIM: the LinUCB kernels' limit on the feat
 LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (the matrix lives in one workgroup's registers)
 LSTM_MAX_HIDDEN, LSTM_MAX_LAYERS = 256, 4  # RG_LSTM_MAX_HIDDEN, RG_LSTM_MAX_LAYERS: the LSTM kernels' limits
 MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
+STEP_CE_MAX_CLASSES = 32  # RG_STEP_CE_MAX_CLASSES: rg_step_ce_head's limit (Seq2Reward's multi_steps)
 CB_LOSS = {"mse": 0, "mae": 1, "cross_entropy": 2}  # RG_CB_LOSS_*: rg_drlinucb_head's losses under the reference's LOSS_TYPES names
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
@@ -346,6 +347,12 @@ SIGNATURES = {
                     + [c_void_p, c_i64] + [c_void_p] * 4 + [c_void_p]),
     "rg_mdn_outputs": (c_int, [c_void_p, c_i64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "rg_mdn_gmm_nll": (c_int, [c_void_p] * 4 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "rg_lstm_fanout_step": (c_int, [c_void_p] * 3 + [c_int] + [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2 + [c_void_p]),
+    "rg_seq2reward_plan_max": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p, c_void_p]),
+    "rg_seq2reward_head_partials": (c_int, [c_int]),
+    "rg_seq2reward_head": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 6 + [c_void_p]),
+    "rg_step_ce_head_partials": (c_int, [c_int]),
+    "rg_step_ce_head": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4 + [c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Parameter dataclasses with the field names / defaults of reagent/core/parameters.py
-(SlateOptParameters :33-43, RLParameters :46-67, MDNRNNTrainerParameters :70-85, EvaluationParameters :118-120, NormalizationParameters :138-152).
+(SlateOptParameters :33-43, RLParameters :46-67, MDNRNNTrainerParameters :70-85, Seq2RewardTrainerParameters :88-99, EvaluationParameters :118-120, NormalizationParameters :138-152).
 Objects of the reference's own classes are accepted anywhere these are (duck typing)."""
 import enum
 from dataclasses import dataclass, field
@@ -53,6 +53,18 @@ class MDNRNNTrainerParameters:
     action_dim: int = 2
     action_names: Optional[List[str]] = None
     multi_steps: int = 1
+
+
+@dataclass(frozen=True)
+class Seq2RewardTrainerParameters:
+    learning_rate: float = 0.001
+    multi_steps: int = 1
+    action_names: List[str] = field(default_factory=lambda: [])
+    compress_model_learning_rate: float = 0.001
+    gamma: float = 1.0
+    view_q_value: bool = False
+    step_predict_net_size: int = 64
+    reward_boost: Optional[Dict[str, float]] = None  # carried, unused (as in the reference's trainer)
 
 
 @dataclass(frozen=True)

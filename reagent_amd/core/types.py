@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -404,7 +404,7 @@ class MemoryNetworkInput(BaseInput):
     """:1017-1046 — the world model's batch: every tensor sequence first, [seq_len, batch, ...]"""
 
     action: FeatureData
-    valid_step: Optional[torch.Tensor] = None  # carried, unused (as in the reference's trainer)
+    valid_step: Optional[torch.Tensor] = None  # [B, 1] int64 in 1 .. seq_len: read by the Seq2Reward trainers alone
     extras: ExtraData = field(default_factory=ExtraData)
 
     @classmethod
@@ -443,6 +443,13 @@ class MemoryNetworkOutput(TensorDataClass):
     all_steps_lstm_hidden: torch.Tensor
 
 
+@dataclass
+class Seq2RewardOutput(TensorDataClass):
+    """:1069-1071"""
+
+    acc_reward: torch.Tensor
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -465,7 +472,7 @@ _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
                   "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput", "MemoryNetworkInput",
-                  "MemoryNetworkOutput"):
+                  "MemoryNetworkOutput", "Seq2RewardOutput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

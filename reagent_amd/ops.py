@@ -758,6 +758,90 @@ def mdn_gmm_nll(batch, mus, sigmas, logpi, nll):
                                         L.stream_ptr()))
 
 
+# ---- world model (Seq2Reward) -----------------------------------------------------------------------------------
+def lstm_fanout_step(h_prev, c_prev, proj, from_table: bool, w_hh, b_hh, fanout: int, h, c):
+    """one LSTM layer's single step over the parents * fanout children of a prefix-tree level (see rg_lstm_fanout_step): child
+    r continues row r // fanout of h_prev / c_prev [parents, H] (c_prev None: zeros); its input projection is row r %
+    proj.shape[0] of proj (from_table) or row r of proj [parents * fanout, 4H]"""
+    _chk_dev(h_prev, c_prev, proj, w_hh, b_hh, h, c)
+    parents, H = h_prev.shape
+    n = parents * int(fanout)
+    if H > L.LSTM_MAX_HIDDEN:
+        raise NotImplementedError(f"LSTM kernels: hidden size {H} is not supported (1 .. {L.LSTM_MAX_HIDDEN})")
+    if n >= 1 << 29:
+        raise NotImplementedError(f"LSTM kernels: {n} child rows are not supported (below 2^29)")
+    assert parents >= 1 and fanout >= 1 and H >= 1 and w_hh.shape == (4 * H, H) and proj.shape[1] == 4 * H
+    assert from_table or proj.shape[0] == n
+    _f32_flat(h_prev, parents * H), _f32_flat(c_prev, parents * H), _f32_flat(proj, proj.shape[0] * 4 * H)
+    _f32_flat(w_hh, 4 * H * H), _f32_flat(b_hh, 4 * H), _f32_flat(h, n * H), _f32_flat(c, n * H)
+    _run("rg_lstm_fanout_step", dict(N=n, H=H, fanout=int(fanout), table=bool(from_table)),
+         lambda: L.lib().rg_lstm_fanout_step(L.ptr(h_prev), L.ptr(c_prev), L.ptr(proj), proj.shape[0] if from_table else 0,
+                                             L.ptr(w_hh), L.ptr(b_hh), parents, int(fanout), H, L.ptr(h), L.ptr(c),
+                                             L.stream_ptr()))
+
+
+def seq2reward_plan_max(h, w, bias, group_size: int, q):
+    """q [groups] = max over each group of group_size consecutive rows of h [groups * group_size, H] of h @ w + bias (see
+    rg_seq2reward_plan_max); w [H] and bias [1] are lstm_linear's"""
+    _chk_dev(h, w, bias, q)
+    n, H = h.shape
+    groups = n // int(group_size)
+    if n >= 1 << 29:
+        raise NotImplementedError(f"seq2reward_plan_max: {n} leaf rows are not supported (below 2^29)")
+    assert groups >= 1 and groups * group_size == n
+    _f32_flat(h, n * H), _f32_flat(w, H), _f32_flat(bias, 1), _f32_flat(q, groups)
+    _run("rg_seq2reward_plan_max", dict(groups=groups, size=int(group_size), H=H),
+         lambda: L.lib().rg_seq2reward_plan_max(L.ptr(h), L.ptr(w), L.ptr(bias), groups, int(group_size), H, L.ptr(q),
+                                                L.stream_ptr()))
+
+
+def seq2reward_head_partials(batch: int) -> int:
+    return int(L.lib().rg_seq2reward_head_partials(batch))
+
+
+def seq2reward_head(h_all, valid_step, reward, gamma_pow, w, bias, acc_reward, dh_all=None, dw=None, dbias=None, partials=None,
+                    loss=None):
+    """lstm_linear at each row's valid step, the discounted target, the mse loss and its gradients (see rg_seq2reward_head);
+    valid_step [B] int64 is clamped into [1, T] by the kernel (None: the last step); dh_all=None: acc_reward alone"""
+    _chk_dev(h_all, valid_step, reward, gamma_pow, w, bias, acc_reward, dh_all, dw, dbias, partials, loss)
+    T, B, H = h_all.shape
+    if T * B >= 1 << 29:
+        raise NotImplementedError(f"seq2reward_head: seq_len * batch = {T * B} is not supported (below 2^29)")
+    _f32_flat(h_all, T * B * H), _f32_flat(w, H), _f32_flat(bias, 1), _f32_flat(acc_reward, B)
+    if valid_step is not None:
+        assert valid_step.dtype == torch.int64 and valid_step.is_contiguous() and valid_step.numel() == B
+    if dh_all is not None:
+        assert reward is not None and gamma_pow is not None and dw is not None and dbias is not None and loss is not None
+        _f32_flat(reward, T * B), _f32_flat(gamma_pow, T), _f32_flat(dh_all, T * B * H), _f32_flat(dw, H), _f32_flat(dbias, 1)
+        _f32_flat(loss, 1)
+        assert partials.dtype == torch.float64 and partials.is_contiguous()
+        assert partials.numel() >= (H + 2) * seq2reward_head_partials(B)
+    _run("rg_seq2reward_head", dict(T=T, B=B, H=H, train=dh_all is not None),
+         lambda: L.lib().rg_seq2reward_head(L.ptr(h_all), L.ptr(valid_step), L.ptr(reward), L.ptr(gamma_pow), L.ptr(w),
+                                            L.ptr(bias), T, B, H, L.ptr(acc_reward), L.ptr(dh_all), L.ptr(dw), L.ptr(dbias),
+                                            L.ptr(partials), L.ptr(loss), L.stream_ptr()))
+
+
+def step_ce_head_partials(batch: int) -> int:
+    return int(L.lib().rg_step_ce_head_partials(batch))
+
+
+def step_ce_head(logits, valid_step, dlogits=None, softmax=None, partials=None, loss=None):
+    """mean cross-entropy of logits [B, K] against valid_step - 1 (clamped into [0, K - 1]), d loss / d logits and (optional)
+    the softmax (see rg_step_ce_head); valid_step=None: the softmax alone"""
+    _chk_dev(logits, valid_step, dlogits, softmax, partials, loss)
+    B, K = logits.shape
+    if K > L.STEP_CE_MAX_CLASSES:
+        raise NotImplementedError(f"step_ce_head: {K} classes are not supported (1 .. {L.STEP_CE_MAX_CLASSES})")
+    _f32_flat(logits, B * K), _f32_flat(dlogits, B * K), _f32_flat(softmax, B * K), _f32_flat(loss, 1)
+    if valid_step is not None:
+        assert valid_step.dtype == torch.int64 and valid_step.is_contiguous() and valid_step.numel() == B
+        assert partials.dtype == torch.float64 and partials.is_contiguous() and partials.numel() >= step_ce_head_partials(B)
+    _run("rg_step_ce_head", dict(B=B, K=K, train=valid_step is not None),
+         lambda: L.lib().rg_step_ce_head(L.ptr(logits), L.ptr(valid_step), B, K, L.ptr(dlogits), L.ptr(softmax),
+                                         L.ptr(partials), L.ptr(loss), L.stream_ptr()))
+
+
 def linucb_workspace(batch: int, dim: int, device) -> torch.Tensor:
     """the byte workspace rg_linucb_accumulate asks for at (batch, dim)"""
     n = int(L.lib().rg_linucb_workspace_bytes(int(batch), int(dim)))

@@ -1,7 +1,7 @@
 """Seeded synthetic transition data of SURVEY.md §8(d): the same CPU generator feeds the oracle,
 the parity tests and bench.py (tensors are created on the CPU from a seeded torch.Generator and
 then moved), so reference and HIP paths see identical inputs."""
-from typing import Dict
+from typing import Dict, Optional
 
 import numpy as np
 
@@ -205,6 +205,38 @@ def to_memory_network_input(d: Dict[str, torch.Tensor], device=None):
 
     return rlt.MemoryNetworkInput.from_dict({k: (v.to(device) if device is not None and v is not None else v)
                                              for k, v in d.items()})
+
+
+def seq2reward_batch(seq_len: int, batch: int, state_dim: int, num_actions: int, seed: int = 0,
+                     max_valid_step: Optional[int] = None) -> Dict[str, torch.Tensor]:
+    """memory_network_batch's keys for the Seq2Reward trainers: action [T, B, A] one-hot, valid_step [B, 1] int64 in 1 ..
+    seq_len (mixed: both ends occur once the batch allows; 1 .. max_valid_step when given: the step predictor has
+    multi_steps classes, which may be fewer than seq_len), and a reward [T, B] that depends on the first state and on the
+    actions taken (a fixed random score per (state feature, action) plus a per-action offset plus noise), so that planning
+    over actions has something to find"""
+    g = torch.Generator().manual_seed(seed)
+    T, B, S, A = seq_len, batch, state_dim, num_actions
+    top = T if max_valid_step is None else min(T, int(max_valid_step))
+    state = torch.randn(T, B, S, generator=g)
+    next_state = torch.randn(T, B, S, generator=g)
+    idx = torch.randint(0, A, (T, B), generator=g)
+    action = (idx.unsqueeze(-1) == torch.arange(A)).float()
+    score = torch.randn(S, A, generator=g) / S ** 0.5
+    offset = torch.randn(A, generator=g)
+    reward = ((state[0] @ score).unsqueeze(0).expand(T, B, A).gather(2, idx.unsqueeze(-1)).squeeze(-1) + offset[idx]
+              + 0.1 * torch.randn(T, B, generator=g))
+    valid_step = torch.randint(1, top + 1, (B, 1), generator=g)
+    if B >= 2:
+        valid_step[0, 0], valid_step[-1, 0] = 1, top
+    return dict(state=state, action=action, next_state=next_state, reward=reward.contiguous(),
+                not_terminal=torch.ones(T, B), time_diff=torch.ones(T, B), step=None, valid_step=valid_step)
+
+
+def to_seq2reward_input(d: Dict[str, torch.Tensor], device=None):
+    """MemoryNetworkInput with valid_step (from_dict, as the reference's, does not read it)"""
+    b = to_memory_network_input({k: v for k, v in d.items() if k != "valid_step"}, device)
+    b.valid_step = d["valid_step"].to(device) if device is not None else d["valid_step"]
+    return b
 
 
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
