@@ -1360,6 +1360,90 @@ int rg_step_ce_head_partials(int batch);
 int rg_step_ce_head(const float* logits, const int64_t* valid_step, int batch, int classes, float* dlogits, float* softmax,
                     double* partials, float* loss, rg_stream_t stream);
 
+/* World model: the cross-entropy-method planner (reagent/models/cem_planner.py).  Additive symbols: the ABI number does not
+ * move.  Everything is on the caller's stream; no atomics, no flag a workgroup waits on: two runs give the same bits.
+ *
+ * The planner state `planner_state` is 2 D + 2 doubles on the device: mean [D], var [D], done (0 or 1), iterations run.
+ * Every entry point that takes it (or `done`, a pointer to its done slot, nullable) returns at once, writing nothing, when
+ * done is set: the host enqueues all cem_num_iterations iterations and reads back once (cem_planner.py:233-256's `break`
+ * becomes "later iterations do nothing").
+ *
+ * NOISE.  A draw is Philox4x32-10 (rg_philox.h) with key = seed, counter words (c0, c1) = the low and high half of
+ *   n | iteration << 20 | kind << 52      (n < 2^20: the trajectory solution * E + member, or the solution for kinds 4, 5)
+ * and (c2, c3) = (lo, hi), four 32-bit outputs x0 .. x3:
+ *   kind 0  u_model[n]        (hi, lo) = (0, 0)            kind 3  eps[step, n, s]     (hi, lo) = (step, s)
+ *   kind 1  u_mix[step, n]    (hi, lo) = (step, 0)         kind 4  tn[solution, d]     (hi, lo) = (d, attempt)
+ *   kind 2  u_term[step, n]   (hi, lo) = (step, 0)         kind 5  action[solution, step]  (hi, lo) = (step, 0)
+ * A uniform is fp32 (x0 >> 8) * 2^-24, in [0, 1).  A standard normal is Box-Muller in double,
+ * sqrt(-2 ln((x0 + 1) 2^-32)) cos(2 pi x1 2^-32), rounded once to fp32 for eps and kept in double for tn.  An integer draw
+ * is floor(u * count) in double.  tn is a standard normal truncated to [-2, 2] by rejection: attempt t = 0 .. 31 of an
+ * element, the first inside is taken; after 32 the last is clamped.  rg_cem_fill_noise writes u_model [N], u_mix [T, N],
+ * eps [T, N, S], u_term [T, N] exactly as rg_cem_group and rg_cem_rollout would draw them in place (their noise arguments
+ * NULL); with the buffers passed the results have the same bits.
+ *
+ * rg_cem_group: each trajectory's world model floor(u_model[n] * models) (cem_planner.py:137), then a counting sort by one
+ * workgroup: rowmap [tiles * 32] lists, per tile of 32 rows, trajectories of ONE model in index order (-1: padding),
+ * tile_model [tiles] that model (-1: an unused tile); tiles = rg_cem_rollout_tiles(N, models) = N / 32 + models.  A model
+ * that draws no trajectory gets no tile.
+ *
+ * rg_cem_rollout: acc_rewards_of_all_solutions (:121-190) of population solutions x ensemble trajectories in one launch, a
+ * workgroup per tile for all `horizon` steps.  table [models][3 layers + 2] holds device pointers to each member's
+ * rnn.weight_ih_l*, bias_ih_l*, bias_hh_l* and gmm_linear's weight and bias, read in place.  Per step x = cat([action_j,
+ * state]) (actions first, MDNRNN's order); the action is row j of solutions [P, horizon, A] fp32, or the one-hot of
+ * action_idx [P, horizon] (exactly one of the two is given).
+ * KEPT QUIRK: h and c are ZERO at every planning step (the reference passes no hidden state to mem_net, :197), so W_hh and
+ * the forget gate contribute nothing: pre = x W_ih^T + b_ih + b_hh, c = i * g, h = o * tanh(c), per layer; the products are
+ * k-ordered fp32 chains on v_mfma_f32_32x32x2_f32, the gate arithmetic is rg_lstm_forward's (double, rounded once).
+ * z = gmm_linear(h).  The mixture index is the inverse CDF over softmax(z[2GS .. 2GS + G)) in index order against u_mix
+ * (the count of cumulative sums <= u, at most G - 1); next_state = fp32(mu_k + exp(z_sigma_k) * eps), in double, rounded once;
+ * not_terminal = (u_term < sigmoid(z[-1])) when terminal_effective, else 1.  The reward z[-2] of step j enters as the fp32
+ * product z[-2] * gamma_pow[j] (gamma_pow [horizon] = fp32(gamma ** j) from the host), summed in double in step order; the
+ * step at which a terminal is sampled counts, nothing after it does.  A stopped trajectory stays in its tile's barriers
+ * and products, masked.  out [population]: the trajectory's sum for ensemble == 1; for ensemble > 1 the mean over the
+ * solution's trajectories in double in index order (traj [N] is then the per-trajectory workspace).  DEPARTURE: the
+ * reference assigns the length-E array to a scalar slot (:186) and raises for E > 1.
+ * trace (nullable; for tests) [T, N, S + W + 2] with W = (2S + 1)G + 2 holds per step and trajectory the state it entered
+ * with, its z row, the sampled index and not_terminal (as floats).  When NULL the launch writes out (and traj) alone.
+ * RG_EUNSUPPORTED for hidden > RG_LSTM_MAX_HIDDEN, layers > RG_LSTM_MAX_LAYERS, num_gaussians > RG_MDN_MAX_GAUSSIANS,
+ * state_dim + action_dim > RG_CEM_MAX_INPUT, models > RG_CEM_MAX_MODELS, horizon > RG_CEM_MAX_HORIZON or
+ * population * ensemble >= RG_CEM_MAX_TRAJECTORIES.  rg_cem_rollout_lds_bytes is the launch's dynamic LDS request.
+ *
+ * rg_cem_sample: solutions [P, D] = tn * sqrt(constrained_variance(mean, var)) + mean in double (:217-222, :235-242; lower
+ * and upper are the bounds tiled to D), and their fp32 copy (:243-247).  tn [P, D] (nullable) replaces the draw.
+ * rg_cem_sample_discrete: actions [P, horizon] = floor(u * A): random.choices over the enumerated product (:275-278)
+ * without the enumeration.
+ *
+ * rg_cem_refit (:249-255), one workgroup: the elites are the last num_elites entries of np.argsort(rewards) (a NaN ranks
+ * above every number; of equal rewards the higher index ranks higher); per dimension their mean and population variance
+ * in double in solution-index order; mean = alpha mean + (1 - alpha) new_mean, the same for var; iterations run += 1; done
+ * is set when max(var) <= epsilon.  flags [P] is workspace (1: an elite).  RG_EINVAL for num_elites outside [1, P].
+ *
+ * rg_cem_tally (:287-296): out [3 A + 1] = per first action actions[p, 0] the count, the sum of rewards in index order and
+ * their quotient (0 / 0 = NaN: never drawn), then np.nanargmax of the quotients (-1: every quotient is NaN). */
+#define RG_CEM_MAX_MODELS 16
+#define RG_CEM_MAX_HORIZON 64
+#define RG_CEM_MAX_INPUT 512
+#define RG_CEM_MAX_TRAJECTORIES (1 << 20)
+int rg_cem_fill_noise(uint64_t seed, int iteration, int trajectories, int horizon, int state_dim, float* u_model, float* u_mix,
+                      float* eps, float* u_term, rg_stream_t stream);
+int rg_cem_rollout_tiles(int trajectories, int models);
+int rg_cem_group(const float* u_model, uint64_t seed, int iteration, int trajectories, int models, const double* done,
+                 int* rowmap, int* tile_model, rg_stream_t stream);
+size_t rg_cem_rollout_lds_bytes(int state_dim, int action_dim, int hidden);
+int rg_cem_rollout(const float* const* table, int models, const int* rowmap, const int* tile_model, int tiles,
+                   const float* init_state, const float* solutions, const int* action_idx, const float* gamma_pow,
+                   const float* u_mix, const float* eps, const float* u_term, uint64_t seed, int iteration, const double* done,
+                   int population, int ensemble, int horizon, int state_dim, int action_dim, int num_gaussians, int hidden,
+                   int layers, int terminal_effective, double* traj, double* out, float* trace, rg_stream_t stream);
+int rg_cem_sample(const double* planner_state, const double* lower, const double* upper, const double* tn, uint64_t seed,
+                  int iteration, int population, int dims, double* solutions, float* solutions_f32, rg_stream_t stream);
+int rg_cem_sample_discrete(uint64_t seed, int iteration, int population, int horizon, int action_dim, int* actions,
+                           rg_stream_t stream);
+int rg_cem_refit(const double* rewards, const double* solutions, int population, int dims, int num_elites, double alpha,
+                 double epsilon, double* planner_state, int* flags, rg_stream_t stream);
+int rg_cem_tally(const int* actions, int horizon, const double* rewards, int population, int action_dim, double* out,
+                 rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

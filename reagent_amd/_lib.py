@@ -29,6 +29,8 @@ LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (
 LSTM_MAX_HIDDEN, LSTM_MAX_LAYERS = 256, 4  # RG_LSTM_MAX_HIDDEN, RG_LSTM_MAX_LAYERS: the LSTM kernels' limits
 MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
 STEP_CE_MAX_CLASSES = 32  # RG_STEP_CE_MAX_CLASSES: rg_step_ce_head's limit (Seq2Reward's multi_steps)
+CEM_MAX_MODELS, CEM_MAX_HORIZON, CEM_MAX_INPUT = 16, 64, 512  # RG_CEM_MAX_*: the CEM planner kernels' limits
+CEM_MAX_TRAJECTORIES = 1 << 20  # RG_CEM_MAX_TRAJECTORIES: population * ensemble stays below it
 CB_LOSS = {"mse": 0, "mae": 1, "cross_entropy": 2}  # RG_CB_LOSS_*: rg_drlinucb_head's losses under the reference's LOSS_TYPES names
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
@@ -353,6 +355,16 @@ SIGNATURES = {
     "rg_seq2reward_head": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 6 + [c_void_p]),
     "rg_step_ce_head_partials": (c_int, [c_int]),
     "rg_step_ce_head": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4 + [c_void_p]),
+    "rg_cem_fill_noise": (c_int, [ctypes.c_uint64] + [c_int] * 4 + [c_void_p] * 4 + [c_void_p]),
+    "rg_cem_rollout_tiles": (c_int, [c_int, c_int]),
+    "rg_cem_group": (c_int, [c_void_p, ctypes.c_uint64, c_int, c_int, c_int] + [c_void_p] * 3 + [c_void_p]),
+    "rg_cem_rollout_lds_bytes": (c_sz, [c_int] * 3),
+    "rg_cem_rollout": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 7 + [ctypes.c_uint64, c_int, c_void_p]
+                       + [c_int] * 9 + [c_void_p] * 3 + [c_void_p]),
+    "rg_cem_sample": (c_int, [c_void_p] * 4 + [ctypes.c_uint64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "rg_cem_sample_discrete": (c_int, [ctypes.c_uint64] + [c_int] * 4 + [c_void_p, c_void_p]),
+    "rg_cem_refit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_d, c_d, c_void_p, c_void_p, c_void_p]),
+    "rg_cem_tally": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -1,5 +1,5 @@
 """Parameter dataclasses with the field names / defaults of reagent/core/parameters.py
-(SlateOptParameters :33-43, RLParameters :46-67, MDNRNNTrainerParameters :70-85, Seq2RewardTrainerParameters :88-99, EvaluationParameters :118-120, NormalizationParameters :138-152).
+(SlateOptParameters :33-43, RLParameters :46-67, MDNRNNTrainerParameters :70-85, Seq2RewardTrainerParameters :88-99, CEMTrainerParameters :102-115, EvaluationParameters :118-120, NormalizationParameters :138-152).
 Objects of the reference's own classes are accepted anywhere these are (duck typing)."""
 import enum
 from dataclasses import dataclass, field
@@ -65,6 +65,20 @@ class Seq2RewardTrainerParameters:
     view_q_value: bool = False
     step_predict_net_size: int = 64
     reward_boost: Optional[Dict[str, float]] = None  # carried, unused (as in the reference's trainer)
+
+
+@dataclass(frozen=True)
+class CEMTrainerParameters:
+    plan_horizon_length: int = 0
+    num_world_models: int = 0
+    cem_population_size: int = 0
+    cem_num_iterations: int = 0
+    ensemble_population_size: int = 0
+    num_elites: int = 0
+    mdnrnn: MDNRNNTrainerParameters = MDNRNNTrainerParameters()
+    rl: RLParameters = RLParameters()
+    alpha: float = 0.25
+    epsilon: float = 0.001
 
 
 @dataclass(frozen=True)

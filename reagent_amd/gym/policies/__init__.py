@@ -3,3 +3,4 @@
 run in rg_pg_head; the trainers read `sampler.temperature` every step."""
 from .policy import Policy  # noqa: F401
 from .samplers.discrete_sampler import SoftmaxActionSampler  # noqa: F401
+from .cem_policy import CEMPolicy  # noqa: F401

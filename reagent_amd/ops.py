@@ -842,6 +842,147 @@ def step_ce_head(logits, valid_step, dlogits=None, softmax=None, partials=None, 
                                          L.ptr(partials), L.ptr(loss), L.stream_ptr()))
 
 
+# ---- world model (the CEM planner) ---------------------------------------------------------------------------------
+def _typed_flat(t, dtype, numel, what):
+    assert t is None or (t.dtype == dtype and t.is_contiguous() and t.numel() == numel), f"{what}: expected {numel} contiguous {dtype}"
+
+
+def _cem_count_check(n: int, horizon: int = 1):
+    if n >= L.CEM_MAX_TRAJECTORIES:
+        raise NotImplementedError(f"CEM kernels: {n} trajectories are not supported (population * ensemble below 2^20)")
+    if horizon > L.CEM_MAX_HORIZON:
+        raise NotImplementedError(f"CEM kernels: plan_horizon_length {horizon} is not supported (1 .. {L.CEM_MAX_HORIZON})")
+
+
+def cem_fill_noise(seed: int, iteration: int, u_model, u_mix, eps, u_term):
+    """the noise rg_cem_group and rg_cem_rollout would draw in place for (seed, iteration) (see rg_cem_fill_noise): u_model
+    [N], u_mix [T, N], eps [T, N, S], u_term [T, N]"""
+    _chk_dev(u_model, u_mix, eps, u_term)
+    T, N, S = eps.shape
+    _cem_count_check(N, T)
+    _f32_flat(u_model, N), _f32_flat(u_mix, T * N), _f32_flat(eps, T * N * S), _f32_flat(u_term, T * N)
+    _run("rg_cem_fill_noise", dict(N=N, T=T, S=S),
+         lambda: L.lib().rg_cem_fill_noise(int(seed), int(iteration), N, T, S, L.ptr(u_model), L.ptr(u_mix), L.ptr(eps),
+                                           L.ptr(u_term), L.stream_ptr()))
+
+
+def cem_rollout_tiles(trajectories: int, models: int) -> int:
+    return int(L.lib().rg_cem_rollout_tiles(int(trajectories), int(models)))
+
+
+def cem_rollout_lds_bytes(state_dim: int, action_dim: int, hidden: int) -> int:
+    return int(L.lib().rg_cem_rollout_lds_bytes(int(state_dim), int(action_dim), int(hidden)))
+
+
+def cem_group(u_model, seed: int, iteration: int, trajectories: int, models: int, done, rowmap, tile_model):
+    """the trajectories sorted by their world model into tiles of 32 (see rg_cem_group); u_model None: drawn in place"""
+    _chk_dev(u_model, done, rowmap, tile_model)
+    N, M = int(trajectories), int(models)
+    _cem_count_check(N)
+    if not 1 <= M <= L.CEM_MAX_MODELS:
+        raise NotImplementedError(f"CEM kernels: {M} world models are not supported (1 .. {L.CEM_MAX_MODELS})")
+    tiles = cem_rollout_tiles(N, M)
+    _f32_flat(u_model, N)
+    _typed_flat(rowmap, torch.int32, tiles * 32, "rowmap"), _typed_flat(tile_model, torch.int32, tiles, "tile_model")
+    assert done is None or done.dtype == torch.float64
+    _run("rg_cem_group", dict(N=N, M=M),
+         lambda: L.lib().rg_cem_group(L.ptr(u_model), int(seed), int(iteration), N, M, L.ptr(done), L.ptr(rowmap),
+                                      L.ptr(tile_model), L.stream_ptr()))
+
+
+def cem_rollout(table, rowmap, tile_model, init_state, solutions, action_idx, gamma_pow, action_dim: int, num_gaussians: int,
+                hidden: int, terminal_effective: bool, ensemble: int, out, *, traj=None, u_mix=None, eps=None, u_term=None, seed: int = 0,
+                iteration: int = 0, done=None, trace=None):
+    """accumulated rewards of every solution (see rg_cem_rollout).  table [M, 3 L + 2] int64 holds the members' parameter
+    pointers; solutions [P, T, A] fp32 or action_idx [P, T] int32; trace: None or [T, N, S + W + 2] fp32 (per step and
+    trajectory the entry state, the z row, the sampled index, not_terminal)"""
+    _chk_dev(table, rowmap, tile_model, init_state, solutions, action_idx, gamma_pow, out, traj, u_mix, eps, u_term, done, trace)
+    assert (solutions is None) != (action_idx is None), "one of solutions and action_idx"
+    M, cols = table.shape
+    layers = (cols - 2) // 3
+    S = init_state.numel()
+    if solutions is not None:
+        P, T, A = solutions.shape
+        assert A == int(action_dim), (solutions.shape, action_dim)
+        _f32_flat(solutions, P * T * A)
+    else:
+        P, T = action_idx.shape
+        A = int(action_dim)
+        _typed_flat(action_idx, torch.int32, P * T, "action_idx")
+    E = int(ensemble)
+    N = P * E
+    _cem_count_check(N, T)
+    G, H = int(num_gaussians), int(hidden)
+    W = (2 * S + 1) * G + 2
+    if H > L.LSTM_MAX_HIDDEN or layers > L.LSTM_MAX_LAYERS or G > L.MDN_MAX_GAUSSIANS or S + A > L.CEM_MAX_INPUT:
+        raise NotImplementedError(f"rg_cem_rollout: hidden {H}, layers {layers}, gaussians {G}, state_dim + action_dim {S + A} are not "
+                       f"supported (at most {L.LSTM_MAX_HIDDEN}, {L.LSTM_MAX_LAYERS}, {L.MDN_MAX_GAUSSIANS}, {L.CEM_MAX_INPUT})")
+    tiles = cem_rollout_tiles(N, M)
+    assert table.dtype == torch.int64 and table.is_contiguous() and cols == 3 * layers + 2 and layers >= 1
+    _typed_flat(rowmap, torch.int32, tiles * 32, "rowmap"), _typed_flat(tile_model, torch.int32, tiles, "tile_model")
+    _f32_flat(init_state, S), _f32_flat(gamma_pow, T), _f32_flat(u_mix, T * N), _f32_flat(eps, T * N * S), _f32_flat(u_term, T * N)
+    _typed_flat(out, torch.float64, P, "out"), _typed_flat(traj, torch.float64, N, "traj")
+    assert E == 1 or traj is not None, "ensemble > 1 needs the per-trajectory workspace"
+    assert done is None or done.dtype == torch.float64
+    _f32_flat(trace, T * N * (S + W + 2))
+    _run("rg_cem_rollout", dict(P=P, E=E, T=T, S=S, A=A, G=G, H=H, L=layers, M=M),
+         lambda: L.lib().rg_cem_rollout(L.ptr(table), M, L.ptr(rowmap), L.ptr(tile_model), tiles, L.ptr(init_state),
+                                        L.ptr(solutions), L.ptr(action_idx), L.ptr(gamma_pow), L.ptr(u_mix), L.ptr(eps),
+                                        L.ptr(u_term), int(seed), int(iteration), L.ptr(done), P, E, T, S, A, G, H, layers,
+                                        1 if terminal_effective else 0, L.ptr(traj), L.ptr(out), L.ptr(trace), L.stream_ptr()))
+
+
+def cem_sample(planner_state, lower, upper, seed: int, iteration: int, solutions, solutions_f32, tn=None):
+    """solutions [P, D] = tn * sqrt(constrained_variance(mean, var)) + mean and their fp32 copy (see rg_cem_sample);
+    planner_state [2 D + 2] float64; tn [P, D] float64 replaces the truncated-normal draw"""
+    _chk_dev(planner_state, lower, upper, solutions, solutions_f32, tn)
+    P, D = solutions.shape
+    _cem_count_check(P)
+    f64 = torch.float64
+    _typed_flat(planner_state, f64, 2 * D + 2, "planner_state"), _typed_flat(lower, f64, D, "lower"), _typed_flat(upper, f64, D, "upper")
+    _typed_flat(solutions, f64, P * D, "solutions"), _f32_flat(solutions_f32, P * D), _typed_flat(tn, f64, P * D, "tn")
+    _run("rg_cem_sample", dict(P=P, D=D),
+         lambda: L.lib().rg_cem_sample(L.ptr(planner_state), L.ptr(lower), L.ptr(upper), L.ptr(tn), int(seed), int(iteration), P,
+                                       D, L.ptr(solutions), L.ptr(solutions_f32), L.stream_ptr()))
+
+
+def cem_sample_discrete(seed: int, iteration: int, action_dim: int, actions):
+    """actions [P, T] int32 = floor(u * action_dim) (see rg_cem_sample_discrete)"""
+    _chk_dev(actions)
+    P, T = actions.shape
+    _cem_count_check(P, T)
+    _typed_flat(actions, torch.int32, P * T, "actions")
+    _run("rg_cem_sample_discrete", dict(P=P, T=T, A=int(action_dim)),
+         lambda: L.lib().rg_cem_sample_discrete(int(seed), int(iteration), P, T, int(action_dim), L.ptr(actions), L.stream_ptr()))
+
+
+def cem_refit(rewards, solutions, num_elites: int, alpha: float, epsilon: float, planner_state, flags):
+    """the elites' mean and variance folded into planner_state, the iteration count and the done flag (see rg_cem_refit)"""
+    _chk_dev(rewards, solutions, planner_state, flags)
+    P, D = solutions.shape
+    _cem_count_check(P)
+    if not 1 <= int(num_elites) <= P:
+        raise ValueError(f"num_elites {num_elites} is outside [1, cem_population_size = {P}]")
+    f64 = torch.float64
+    _typed_flat(rewards, f64, P, "rewards"), _typed_flat(solutions, f64, P * D, "solutions")
+    _typed_flat(planner_state, f64, 2 * D + 2, "planner_state"), _typed_flat(flags, torch.int32, P, "flags")
+    _run("rg_cem_refit", dict(P=P, D=D, elites=int(num_elites)),
+         lambda: L.lib().rg_cem_refit(L.ptr(rewards), L.ptr(solutions), P, D, int(num_elites), float(alpha), float(epsilon),
+                                      L.ptr(planner_state), L.ptr(flags), L.stream_ptr()))
+
+
+def cem_tally(actions, rewards, action_dim: int, out):
+    """per first action the count, the reward sum and their quotient, then np.nanargmax (see rg_cem_tally): out [3 A + 1]"""
+    _chk_dev(actions, rewards, out)
+    P, T = actions.shape
+    A = int(action_dim)
+    _cem_count_check(P)
+    _typed_flat(actions, torch.int32, P * T, "actions"), _typed_flat(rewards, torch.float64, P, "rewards")
+    _typed_flat(out, torch.float64, 3 * A + 1, "out")
+    _run("rg_cem_tally", dict(P=P, A=A),
+         lambda: L.lib().rg_cem_tally(L.ptr(actions), T, L.ptr(rewards), P, A, L.ptr(out), L.stream_ptr()))
+
+
 def linucb_workspace(batch: int, dim: int, device) -> torch.Tensor:
     """the byte workspace rg_linucb_accumulate asks for at (batch, dim)"""
     n = int(L.lib().rg_linucb_workspace_bytes(int(batch), int(dim)))

@@ -9,6 +9,7 @@ from .parametric_dqn_trainer import ParametricDQNTrainer  # noqa: F401
 from .slate_q_trainer import NextSlateValueNormMethod, SlateQTrainer  # noqa: F401
 from .reinforce_trainer import ReinforceTrainer  # noqa: F401
 from .ppo_trainer import PPOTrainer  # noqa: F401
+from .cem_trainer import CEMTrainer  # noqa: F401
 from .cb import DeepRepresentLinUCBTrainer, DisjointLinUCBTrainer, LinUCBTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
