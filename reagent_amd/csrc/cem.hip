@@ -260,29 +260,13 @@ __global__ void RG_LAUNCH_BOUNDS(CEM_THREADS, 1) cem_rollout_kernel(const CemRol
         const int u = tile * LSTM_TILE + col;
         const bool u_ok = u < H;
         const int uc = u_ok ? u : H - 1;
-        const float* wi = w_ih + uc * K;  // (4 H K floats at most 2^19: int offsets)
-        const float* wc = wi + 2 * H * K;
-        const float* wo = wi + 3 * H * K;
-        f32x16 ai, ag, ao;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) ai[r] = 0.f, ag[r] = 0.f, ao[r] = 0.f;
-#pragma unroll 4
-        for (int k = 0; k < Kp; k += 2) {
-          const int kk = k + half;
-          const bool ok = u_ok && kk < K;
-          const int kc = kk < K ? kk : 0;
-          const float av = src[col * pitch + kk];
-          const float bi = wi[kc], bc = wc[kc], bo = wo[kc];
-          ai = mfma_32x32x2_f32(av, ok ? bi : 0.f, ai);
-          ag = mfma_32x32x2_f32(av, ok ? bc : 0.f, ag);
-          ao = mfma_32x32x2_f32(av, ok ? bo : 0.f, ao);
-        }
+        const LstmGates p = lstm_gate_products<false>(src, pitch, w_ih, H, K, Kp, uc, u_ok, col, half);
         const double bi0 = (double)b_ih[uc], bi1 = (double)b_hh[uc];
         const double bg0 = (double)b_ih[2 * H + uc], bg1 = (double)b_hh[2 * H + uc];
         const double bo0 = (double)b_ih[3 * H + uc], bo1 = (double)b_hh[3 * H + uc];
 #pragma unroll 1
         for (int q = 0; q < 4; ++q) {
-          const f32x4 qi = lstm_acc_quad(ai, q), qg = lstm_acc_quad(ag, q), qo = lstm_acc_quad(ao, q);
+          const f32x4 qi = lstm_acc_quad(p.i, q), qg = lstm_acc_quad(p.g, q), qo = lstm_acc_quad(p.o, q);
 #pragma unroll
           for (int jj = 0; jj < 4; ++jj) {
             const int rl = lstm_acc_row(4 * q + jj, half);

@@ -8,7 +8,7 @@
 // fp32 accumulators and is rounded once where it is stored.  Trip counts depend on H alone, a row's bits on that row alone.
 #include <rg_platform.h>
 #include "../../include/reagent_hip.h"
-#include "rg_lstm_cell.h"  // the tile shape, lstm_exp / lstm_sigmoid / lstm_tanh, lstm_acc_row / lstm_acc_quad
+#include "rg_lstm_cell.h"  // the tile shape, lstm_gate_products / lstm_gates / lstm_cell, lstm_tanh, lstm_acc_row / lstm_acc_quad
 
 namespace rg {
 
@@ -42,31 +42,13 @@ __global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) lstm_forward_kernel(const Lstm
       const int u = tile * LSTM_TILE + col;
       const bool u_ok = u < H;
       const int uc = u_ok ? u : H - 1;
-      const float* wi = a.w_hh + (long)uc * H;
-      const float* wf = wi + (long)H * H;
-      const float* wg = wf + (long)H * H;
-      const float* wo = wg + (long)H * H;
-      f32x16 ai, af, ag, ao;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) ai[r] = 0.f, af[r] = 0.f, ag[r] = 0.f, ao[r] = 0.f;
-#pragma unroll 4
-      for (int k = 0; k < Hp; k += 2) {
-        const int kk = k + half;  // (< Hp: Hp is even)
-        const bool ok = u_ok && kk < H;
-        const int kc = kk < H ? kk : 0;
-        const float av = cur[col * pitch + kk];
-        const float bi = wi[kc], bf = wf[kc], bg = wg[kc], bo = wo[kc];
-        ai = mfma_32x32x2_f32(av, ok ? bi : 0.f, ai);
-        af = mfma_32x32x2_f32(av, ok ? bf : 0.f, af);
-        ag = mfma_32x32x2_f32(av, ok ? bg : 0.f, ag);
-        ao = mfma_32x32x2_f32(av, ok ? bo : 0.f, ao);
-      }
+      const LstmGates p = lstm_gate_products(cur, pitch, a.w_hh, H, H, Hp, uc, u_ok, col, half);
       double bias[4];
 #pragma unroll
       for (int g = 0; g < 4; ++g) bias[g] = a.b_hh ? (double)a.b_hh[g * H + uc] : 0.0;
 #pragma unroll 1
       for (int q = 0; q < 4; ++q) {  // four rows at a time: the double arithmetic below is compiled once, not sixteen times
-        const f32x4 qi = lstm_acc_quad(ai, q), qf = lstm_acc_quad(af, q), qg = lstm_acc_quad(ag, q), qo = lstm_acc_quad(ao, q);
+        const f32x4 qi = lstm_acc_quad(p.i, q), qf = lstm_acc_quad(p.f, q), qg = lstm_acc_quad(p.g, q), qo = lstm_acc_quad(p.o, q);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int rl = lstm_acc_row(4 * q + j, half);
@@ -75,22 +57,18 @@ __global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) lstm_forward_kernel(const Lstm
           const long rowc = row < B ? row : B - 1;  // (addresses stay inside the arrays; the values are dropped)
           const long at = ((long)t * B + rowc) * H + uc;
           const float* xp = a.xproj + ((long)t * B + rowc) * 4 * H + uc;
-          const double gi = lstm_sigmoid((double)qi[j] + (double)xp[0] + bias[0], ec);
-          const double gf = lstm_sigmoid((double)qf[j] + (double)xp[H] + bias[1], ec);
-          const double gg = lstm_tanh((double)qg[j] + (double)xp[2 * H] + bias[2], ec);
-          const double go = lstm_sigmoid((double)qo[j] + (double)xp[3 * H] + bias[3], ec);
+          LstmCell e = lstm_gates(qi[j], qf[j], qg[j], qo[j], xp, H, bias, ec);
           const float cp = t == 0 ? (a.c0 ? a.c0[rowc * H + uc] : 0.f) : a.c_all[at - (long)B * H];
-          const float c = (float)(gf * (double)cp + gi * gg);
-          const float h = (float)(go * lstm_tanh((double)c, ec));  // of the stored c: the backward takes tanh of the same value
+          lstm_cell(e, cp, ec);
           if (ok) {
-            a.h_all[at] = h;
-            a.c_all[at] = c;
+            a.h_all[at] = e.h;
+            a.c_all[at] = e.c;
             if (a.gates) {
               float* gp = a.gates + ((long)t * B + row) * 4 * H + u;
-              gp[0] = (float)gi, gp[H] = (float)gf, gp[2 * H] = (float)gg, gp[3 * H] = (float)go;
+              gp[0] = (float)e.gi, gp[H] = (float)e.gf, gp[2 * H] = (float)e.gg, gp[3 * H] = (float)e.go;
             }
           }
-          nxt[rl * pitch + u] = ok ? h : 0.f;
+          nxt[rl * pitch + u] = ok ? e.h : 0.f;
         }
       }
     }

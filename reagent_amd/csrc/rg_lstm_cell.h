@@ -1,7 +1,13 @@
-// rg_lstm_cell.h — what the LSTM kernels of lstm.hip (a layer over a whole sequence) and seq2reward.hip (a layer's single
-// step over the children of a prefix tree) share: the tile shape, the gate arithmetic's exp / sigmoid / tanh in double with
-// their constants in LDS, and the accumulator layout of v_mfma_f32_32x32x2_f32.  Both files compute a cell from the same
-// functions on the same operands in the same order, so a step gives the same bits in either.
+// rg_lstm_cell.h — the LSTM cell of the recurrent kernels, written once: the tile shape, the accumulator layout of
+// v_mfma_f32_32x32x2_f32, the gate products (lstm_gate_products), the gate arithmetic's exp / sigmoid / tanh in double with
+// their constants in LDS, the gates and the cell update (lstm_gates, lstm_cell).  lstm_forward_kernel (lstm.hip: a layer
+// over a whole sequence), s2r_fanout_kernel (seq2reward.hip: a layer's single step over the children of a prefix tree) and
+// cem_rollout_kernel (cem.hip: the planner's layers from a zero state) call the same product function; the first two call
+// the same gate and cell functions, so a step has the same bits in either because it is the same code.  The rollout's cell
+// is the zero-state special case and stays in cem.hip: with h = c = 0 it never forms the forget gate
+// (lstm_gate_products<false> skips its row), adds both biases to the products of W_ih, ((acc + b_ih) + b_hh), and takes
+// c = i * g.  lstm_cell with c_{t-1} = 0 is not that: f * 0 + i * g is +0 where i * g is -0, and NaN where the forget
+// pre-activation is NaN, which the rollout never computes.  What stays in each kernel is its row addressing and its stores.
 #pragma once
 #include <rg_platform.h>
 
@@ -61,6 +67,61 @@ __device__ __forceinline__ f32x4 lstm_acc_quad(const f32x16& v, int q) {
     default: o[0] = v[12], o[1] = v[13], o[2] = v[14], o[3] = v[15]; break;
   }
   return o;
+}
+
+// The i, f, g, o products of one 32 x 32 tile: src [32 rows, K] (LDS, pitch) times rows uc, H + uc, 2H + uc, 3H + uc of
+// w [4H, K] (global; one row per lane's column), exact fp32 products accumulated in k order.  A masked column (u_ok false, uc
+// clamped) and the k past K multiply zeros; Kp is K rounded up to even.  WITH_F = false leaves the forget gate's row unread.
+struct LstmGates {
+  f32x16 i, f, g, o;
+};
+template <bool WITH_F = true>
+__device__ __forceinline__ LstmGates lstm_gate_products(const float* src, int pitch, const float* w, int H, int K, int Kp,
+                                                        int uc, bool u_ok, int col, int half) {
+  const float* wi = w + (long)uc * K;
+  const float* wf = wi + (long)H * K;
+  const float* wg = wf + (long)H * K;
+  const float* wo = wg + (long)H * K;
+  f32x16 zero;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) zero[r] = 0.f;
+  LstmGates a = {zero, zero, zero, zero};
+#pragma unroll 4
+  for (int k = 0; k < Kp; k += 2) {
+    const int kk = k + half;  // (< Kp: Kp is even)
+    const bool ok = u_ok && kk < K;
+    const int kc = kk < K ? kk : 0;
+    const float av = src[col * pitch + kk];
+    const float bi = wi[kc], bf = WITH_F ? wf[kc] : 0.f, bg = wg[kc], bo = wo[kc];
+    a.i = mfma_32x32x2_f32(av, ok ? bi : 0.f, a.i);
+    if (WITH_F) a.f = mfma_32x32x2_f32(av, ok ? bf : 0.f, a.f);
+    a.g = mfma_32x32x2_f32(av, ok ? bg : 0.f, a.g);
+    a.o = mfma_32x32x2_f32(av, ok ? bo : 0.f, a.o);
+  }
+  return a;
+}
+
+// One element's cell in two calls, between which the kernel reads c_{t-1}.  lstm_gates: from the four products p*, the input
+// projection xp[g * H] and bias[g], (i, f, o) = sigmoid, g = tanh.  lstm_cell: c = f * c_{t-1} + i * g, h = o * tanh(c) of the
+// stored c (the backward takes tanh of the same value).  Two calls because of where the c_{t-1} load lands: read before the
+// gates, it is issued and waited for ahead of the four xp loads (one more exposed memory latency per row quad, 1.4 % of
+// rg_lstm_forward at 32 workgroups); read between the calls it is in flight with them, as in the kernels before the sharing.
+struct LstmCell {
+  double gi, gf, gg, go;
+  float c, h;
+};
+__device__ __forceinline__ LstmCell lstm_gates(float pi, float pf, float pg, float po, const float* xp, int H,
+                                               const double* bias, const double* ec) {
+  LstmCell r;
+  r.gi = lstm_sigmoid((double)pi + (double)xp[0] + bias[0], ec);
+  r.gf = lstm_sigmoid((double)pf + (double)xp[H] + bias[1], ec);
+  r.gg = lstm_tanh((double)pg + (double)xp[2 * H] + bias[2], ec);
+  r.go = lstm_sigmoid((double)po + (double)xp[3 * H] + bias[3], ec);
+  return r;
+}
+__device__ __forceinline__ void lstm_cell(LstmCell& r, float cp, const double* ec) {
+  r.c = (float)(r.gf * (double)cp + r.gi * r.gg);
+  r.h = (float)(r.go * lstm_tanh((double)r.c, ec));
 }
 
 static inline int lstm_padded(int H) { return (H + LSTM_TILE - 1) / LSTM_TILE * LSTM_TILE; }

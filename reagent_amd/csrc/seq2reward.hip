@@ -45,31 +45,13 @@ __global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) s2r_fanout_kernel(const Fanout
     const int u = tile * LSTM_TILE + col;
     const bool u_ok = u < H;
     const int uc = u_ok ? u : H - 1;
-    const float* wi = a.w_hh + (long)uc * H;
-    const float* wf = wi + (long)H * H;
-    const float* wg = wf + (long)H * H;
-    const float* wo = wg + (long)H * H;
-    f32x16 ai, af, ag, ao;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) ai[r] = 0.f, af[r] = 0.f, ag[r] = 0.f, ao[r] = 0.f;
-#pragma unroll 4
-    for (int k = 0; k < Hp; k += 2) {
-      const int kk = k + half;  // (< Hp: Hp is even)
-      const bool ok = u_ok && kk < H;
-      const int kc = kk < H ? kk : 0;
-      const float av = cur[col * pitch + kk];
-      const float bi = wi[kc], bf = wf[kc], bg = wg[kc], bo = wo[kc];
-      ai = mfma_32x32x2_f32(av, ok ? bi : 0.f, ai);
-      af = mfma_32x32x2_f32(av, ok ? bf : 0.f, af);
-      ag = mfma_32x32x2_f32(av, ok ? bg : 0.f, ag);
-      ao = mfma_32x32x2_f32(av, ok ? bo : 0.f, ao);
-    }
+    const LstmGates p = lstm_gate_products(cur, pitch, a.w_hh, H, H, Hp, uc, u_ok, col, half);
     double bias[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) bias[g] = a.b_hh ? (double)a.b_hh[g * H + uc] : 0.0;
 #pragma unroll 1
     for (int q = 0; q < 4; ++q) {
-      const f32x4 qi = lstm_acc_quad(ai, q), qf = lstm_acc_quad(af, q), qg = lstm_acc_quad(ag, q), qo = lstm_acc_quad(ao, q);
+      const f32x4 qi = lstm_acc_quad(p.i, q), qf = lstm_acc_quad(p.f, q), qg = lstm_acc_quad(p.g, q), qo = lstm_acc_quad(p.o, q);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const long row = row0 + lstm_acc_row(4 * q + j, half);
@@ -77,16 +59,12 @@ __global__ void RG_LAUNCH_BOUNDS(LSTM_THREADS, 1) s2r_fanout_kernel(const Fanout
         const long rowc = row < N ? row : N - 1;  // (addresses stay inside the arrays; the values are dropped)
         const long prow = a.table_rows > 0 ? rowc % a.table_rows : rowc;
         const float* xp = a.proj + prow * 4 * H + uc;
-        const double gi = lstm_sigmoid((double)qi[j] + (double)xp[0] + bias[0], ec);
-        const double gf = lstm_sigmoid((double)qf[j] + (double)xp[H] + bias[1], ec);
-        const double gg = lstm_tanh((double)qg[j] + (double)xp[2 * H] + bias[2], ec);
-        const double go = lstm_sigmoid((double)qo[j] + (double)xp[3 * H] + bias[3], ec);
+        LstmCell e = lstm_gates(qi[j], qf[j], qg[j], qo[j], xp, H, bias, ec);
         const float cp = a.c_prev ? a.c_prev[rowc / a.fanout * H + uc] : 0.f;
-        const float c = (float)(gf * (double)cp + gi * gg);
-        const float h = (float)(go * lstm_tanh((double)c, ec));
+        lstm_cell(e, cp, ec);
         if (ok) {
-          a.h[rowc * H + uc] = h;
-          a.c[rowc * H + uc] = c;
+          a.h[rowc * H + uc] = e.h;
+          a.c[rowc * H + uc] = e.c;
         }
       }
     }

@@ -32,6 +32,7 @@ from .. import ops
 from ..core import types as rlt
 from ..core.parameters import CONTINUOUS_TRAINING_ACTION_RANGE
 from ..preprocessing.trainer_preprocessor import rescale_actions
+from . import lstm_stack
 from .world_model import MemoryNetwork
 
 F32, F64, I32 = torch.float32, torch.float64, torch.int32
@@ -125,7 +126,7 @@ class CEMPlannerNetwork(nn.Module):
         net = m.mdnrnn
         out = []
         for k in range(net.num_hidden_layers):
-            w_ih, _w_hh, b_ih, b_hh = net._layer(k)
+            w_ih, _w_hh, b_ih, b_hh = lstm_stack.layer_params(net.rnn, k)
             out += [w_ih, b_ih, b_hh]
         return out + [net.gmm_linear.weight, net.gmm_linear.bias]
 

@@ -18,24 +18,12 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
-from ..engine import _mat, ensure_slab
+from ..engine import ensure_slab
+from . import lstm_stack
+from .lstm_stack import _f32c, _Parameters
 
 F32 = torch.float32
 LINEAR = L.ACT["linear"]
-
-
-class _Parameters(nn.Module):
-    """the parameters of a torch module under their own names, without the module (nothing here runs torch's forward)"""
-
-    def __init__(self, module: nn.Module):
-        super().__init__()
-        for name, p in module.named_parameters():
-            self.register_parameter(name, nn.Parameter(p.detach().clone()))
-
-
-def _f32c(t):
-    t = t if t.dtype == F32 else t.float()
-    return t if t.is_contiguous() else t.contiguous()
 
 
 class MDNRNN(nn.Module):
@@ -63,14 +51,9 @@ class MDNRNN(nn.Module):
         self.num_gaussians = num_gaussians
         self.rnn = _Parameters(nn.LSTM(input_size=state_dim + action_dim, hidden_size=num_hiddens, num_layers=num_hidden_layers))
         self.gmm_linear = _Parameters(nn.Linear(num_hiddens, (2 * state_dim + 1) * num_gaussians + 2))
-        self._wt = {}  # transposed weight copies of the backward's dgrads: name -> (version key, tensor)
+        self._wt = lstm_stack.TransposedWeights()
 
     # ---- the recurrence ----------------------------------------------------------------------------------------------
-    def _layer(self, k):
-        r = self.rnn
-        return (getattr(r, f"weight_ih_l{k}"), getattr(r, f"weight_hh_l{k}"), getattr(r, f"bias_ih_l{k}"),
-                getattr(r, f"bias_hh_l{k}"))
-
     def _run(self, actions, states, hidden=None, save=False):
         """-> the tape of one pass: z [T * B, W] = gmm_linear's output, per layer the input rows, h_all, c_all and (save) the
         gates, and the initial state"""
@@ -87,19 +70,10 @@ class MDNRNN(nn.Module):
             h0, c0 = _f32c(hidden[0].to(dev)), _f32c(hidden[1].to(dev))
             assert h0.shape == c0.shape == (self.num_hidden_layers, B, H), (h0.shape, c0.shape)
         x = _f32c(torch.cat([actions.float(), states.float()], dim=-1)).view(N, -1)
-        tape = dict(T=T, B=B, x=[], h=[], c=[], gates=[], h0=h0, c0=c0)
-        for k in range(self.num_hidden_layers):
-            w_ih, w_hh, b_ih, b_hh = (p.detach() for p in self._layer(k))
-            xproj = torch.empty(N, 4 * H, **f)
-            ops.fc_forward(x, w_ih, b_ih, LINEAR, L.PREC_F32, y32=xproj)
-            h_all, c_all = torch.empty(T, B, H, **f), torch.empty(T, B, H, **f)
-            gates = torch.empty(T, B, 4 * H, **f) if save else None
-            ops.lstm_forward(xproj.view(T, B, 4 * H), w_hh, b_hh, None if h0 is None else h0[k], None if c0 is None else c0[k],
-                             h_all, c_all, gates)
-            tape["x"].append(x), tape["h"].append(h_all), tape["c"].append(c_all), tape["gates"].append(gates)
-            x = h_all.view(N, H)
+        tape = dict(T=T, B=B, h0=h0, c0=c0, **lstm_stack.forward(self.rnn, x, T, B, H, self.num_hidden_layers, h0, c0, save))
         z = torch.empty(N, self.gmm_linear.weight.shape[0], **f)
-        ops.fc_forward(x, self.gmm_linear.weight.detach(), self.gmm_linear.bias.detach(), LINEAR, L.PREC_F32, y32=z)
+        top = tape["h"][-1].view(N, H)
+        ops.fc_forward(top, self.gmm_linear.weight.detach(), self.gmm_linear.bias.detach(), LINEAR, L.PREC_F32, y32=z)
         tape["z"] = z
         return tape
 
@@ -128,15 +102,6 @@ class MDNRNN(nn.Module):
                 torch.zeros(self.num_hidden_layers, batch_size, self.num_hiddens))
 
     # ---- the backward ------------------------------------------------------------------------------------------------
-    def _transposed(self, name, w):
-        key = (w._version, getattr(w, "_rg_version", 0), w.data_ptr())
-        rec = self._wt.get(name)
-        if rec is None or rec[0] != key or rec[1].device != w.device:
-            wt = _mat(w.shape[1], w.shape[0], F32, w.device)
-            ops.transpose_cast(w.detach(), None, wt)
-            rec = self._wt[name] = (key, wt)
-        return rec[1]
-
     def backward(self, tape, dz):
         """d loss / d every parameter from dz = d loss / d gmm_linear's output of a saving pass, written into the parameters'
         gradient slab (the caller publishes it).  Per layer, from the top: rg_lstm_backward, then dW_ih and db_ih =
@@ -147,36 +112,12 @@ class MDNRNN(nn.Module):
         T, B, H = tape["T"], tape["B"], self.num_hiddens
         N, dev = T * B, dz.device
         f = dict(dtype=F32, device=dev)
-
-        def transposed(m):
-            t = _mat(m.shape[1], m.shape[0], F32, dev)
-            ops.transpose_cast(m, None, t)
-            return t
-
-        def wgrad(dzt, xt, w, b):
-            nbytes = ops.fc_wgrad_workspace_bytes(w.shape[0], w.shape[1], N, L.PREC_F32)
-            ws = torch.empty((nbytes + 15) // 16 * 4, **f)
-            ops.fc_wgrad(dzt, xt, grad[id(w)], grad[id(b)], ws, L.PREC_F32)
-
+        transposed = lstm_stack.transposed
         gw, gb = self.gmm_linear.weight, self.gmm_linear.bias
-        wgrad(transposed(dz), transposed(tape["h"][-1].view(N, H)), gw, gb)
+        lstm_stack.wgrad(transposed(dz), transposed(tape["h"][-1].view(N, H)), grad[id(gw)], grad[id(gb)], N)
         dh = torch.empty(N, H, **f)
-        ops.fc_dgrad(dz, self._transposed("gmm", gw), None, LINEAR, L.PREC_F32, dx32=dh)
-        for k in range(self.num_hidden_layers - 1, -1, -1):
-            w_ih, w_hh, b_ih, b_hh = self._layer(k)
-            h0 = None if tape["h0"] is None else tape["h0"][k]
-            c0 = None if tape["c0"] is None else tape["c0"][k]
-            dgates = torch.empty(T, B, 4 * H, **f)
-            ops.lstm_backward(dh.view(T, B, H), tape["gates"][k], tape["c"][k], c0, w_hh.detach(), dgates)
-            dg = dgates.view(N, 4 * H)
-            dgt = transposed(dg)
-            wgrad(dgt, transposed(tape["x"][k]), w_ih, b_ih)
-            first = h0.unsqueeze(0) if h0 is not None else torch.zeros(1, B, H, **f)
-            h_prev = torch.cat([first, tape["h"][k][:-1]], dim=0).view(N, H)
-            wgrad(dgt, transposed(h_prev), w_hh, b_hh)
-            if k > 0:
-                dh = torch.empty(N, H, **f)
-                ops.fc_dgrad(dg, self._transposed(f"ih{k}", w_ih), None, LINEAR, L.PREC_F32, dx32=dh)
+        ops.fc_dgrad(dz, self._wt("gmm", gw), None, LINEAR, L.PREC_F32, dx32=dh)
+        lstm_stack.backward(self.rnn, tape, dh, grad, tape["h0"], tape["c0"], self._wt, want_dh0=False)
         return slab
 
 

@@ -23,9 +23,10 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import ops
 from ..core import types as rlt
-from ..engine import _mat, ensure_slab
+from ..engine import ensure_slab
+from . import lstm_stack
 from .base import ModelBase
-from .mdn_rnn import _f32c, _Parameters
+from .lstm_stack import _f32c, _Parameters
 
 F32 = torch.float32
 LINEAR = L.ACT["linear"]
@@ -47,7 +48,7 @@ class Seq2RewardNetwork(ModelBase):
         self.rnn = _Parameters(nn.LSTM(input_size=action_dim, hidden_size=num_hiddens, num_layers=num_hidden_layers))
         self.lstm_linear = _Parameters(nn.Linear(num_hiddens, 1))
         self.map_linear = _Parameters(nn.Linear(state_dim, self.num_hiddens))
-        self._wt = {}  # transposed weight copies of the backward's dgrads: name -> (version key, tensor)
+        self._wt = lstm_stack.TransposedWeights()
 
     def input_prototype(self):
         return (
@@ -56,11 +57,6 @@ class Seq2RewardNetwork(ModelBase):
         )
 
     # ---- the recurrence ----------------------------------------------------------------------------------------------
-    def _layer(self, k):
-        r = self.rnn
-        return (getattr(r, f"weight_ih_l{k}"), getattr(r, f"weight_hh_l{k}"), getattr(r, f"bias_ih_l{k}"),
-                getattr(r, f"bias_hh_l{k}"))
-
     def _embed(self, state0):
         """map_linear on [B, S] rows -> [B, H]: the initial hidden state of every layer"""
         emb = torch.empty(state0.shape[0], self.num_hiddens, dtype=F32, device=state0.device)
@@ -76,22 +72,11 @@ class Seq2RewardNetwork(ModelBase):
         assert actions.ndim == 3 and states.ndim == 3 and actions.shape[1] == states.shape[1], (actions.shape, states.shape)
         assert actions.shape[2] == self.action_dim and states.shape[2] == self.state_dim
         T, B = actions.shape[0], actions.shape[1]
-        N, H = T * B, self.num_hiddens
-        f = dict(dtype=F32, device=dev)
         state0 = _f32c(states[0])
         emb = self._embed(state0)
-        x = _f32c(actions).view(N, -1)
-        tape = dict(T=T, B=B, state0=state0, emb=emb, x=[], h=[], c=[], gates=[])
-        for k in range(self.num_hidden_layers):
-            w_ih, w_hh, b_ih, b_hh = (p.detach() for p in self._layer(k))
-            xproj = torch.empty(N, 4 * H, **f)
-            ops.fc_forward(x, w_ih, b_ih, LINEAR, L.PREC_F32, y32=xproj)
-            h_all, c_all = torch.empty(T, B, H, **f), torch.empty(T, B, H, **f)
-            gates = torch.empty(T, B, 4 * H, **f) if save else None
-            ops.lstm_forward(xproj.view(T, B, 4 * H), w_hh, b_hh, emb, None, h_all, c_all, gates)
-            tape["x"].append(x), tape["h"].append(h_all), tape["c"].append(c_all), tape["gates"].append(gates)
-            x = h_all.view(N, H)
-        return tape
+        x = _f32c(actions).view(T * B, -1)
+        return dict(T=T, B=B, state0=state0, emb=emb,
+                    **lstm_stack.forward(self.rnn, x, T, B, self.num_hiddens, self.num_hidden_layers, emb, None, save))
 
     def _head_params(self):
         return self.lstm_linear.weight.detach().view(-1), self.lstm_linear.bias.detach()
@@ -136,7 +121,7 @@ class Seq2RewardNetwork(ModelBase):
         B, dev = cur_state.shape[0], cur_state.device
         f = dict(dtype=F32, device=dev)
         emb = self._embed(_f32c(cur_state))
-        layers = [tuple(p.detach() for p in self._layer(k)) for k in range(nl)]
+        layers = [tuple(p.detach() for p in lstm_stack.layer_params(self.rnn, k)) for k in range(nl)]
         table = torch.empty(A, 4 * H, **f)
         ops.fc_forward(torch.eye(A, **f), layers[0][0], layers[0][2], LINEAR, L.PREC_F32, y32=table)
         rows = [B * A ** t for t in range(multi_steps + 1)]
@@ -170,15 +155,6 @@ class Seq2RewardNetwork(ModelBase):
         return per + (4 * H * A ** multi_steps if nl > 1 else 0) + H + A
 
     # ---- the backward ------------------------------------------------------------------------------------------------
-    def _transposed(self, name, w):
-        key = (w._version, getattr(w, "_rg_version", 0), w.data_ptr())
-        rec = self._wt.get(name)
-        if rec is None or rec[0] != key or rec[1].device != w.device:
-            wt = _mat(w.shape[1], w.shape[0], F32, w.device)
-            ops.transpose_cast(w.detach(), None, wt)
-            rec = self._wt[name] = (key, wt)
-        return rec[1]
-
     def backward(self, tape, dh_top, dw_head, db_head):
         """d loss / d every parameter from a saving pass and the head's outputs (dh_top [T, B, H] = d loss / d the top layer's
         h_all, dw_head [H] and db_head [1] = lstm_linear's gradients), written into the parameters' gradient slab (the caller
@@ -189,39 +165,13 @@ class Seq2RewardNetwork(ModelBase):
         params = list(self.parameters())
         slab = ensure_slab(params)
         grad = {id(p): slab.view(slab.grad, i) for i, p in enumerate(params)}
-        T, B, H = tape["T"], tape["B"], self.num_hiddens
-        N, dev = T * B, dh_top.device
-        f = dict(dtype=F32, device=dev)
-
-        def transposed(m):
-            t = _mat(m.shape[1], m.shape[0], F32, dev)
-            ops.transpose_cast(m, None, t)
-            return t
-
-        def wgrad(dzt, xt, w, b, rows):
-            nbytes = ops.fc_wgrad_workspace_bytes(w.shape[0], w.shape[1], rows, L.PREC_F32)
-            ws = torch.empty((nbytes + 15) // 16 * 4, **f)
-            ops.fc_wgrad(dzt, xt, grad[id(w)], grad[id(b)], ws, L.PREC_F32)
-
         grad[id(self.lstm_linear.weight)].view(-1).copy_(dw_head)
         grad[id(self.lstm_linear.bias)].copy_(db_head)
-        dh = dh_top
-        dh0 = [None] * self.num_hidden_layers
-        for k in range(self.num_hidden_layers - 1, -1, -1):
-            w_ih, w_hh, b_ih, b_hh = self._layer(k)
-            dgates = torch.empty(T, B, 4 * H, **f)
-            dh0[k] = torch.empty(B, H, **f)
-            ops.lstm_backward(dh.view(T, B, H), tape["gates"][k], tape["c"][k], None, w_hh.detach(), dgates, dh0[k])
-            dg = dgates.view(N, 4 * H)
-            dgt = transposed(dg)
-            wgrad(dgt, transposed(tape["x"][k]), w_ih, b_ih, N)
-            h_prev = torch.cat([tape["emb"].unsqueeze(0), tape["h"][k][:-1]], dim=0).view(N, H)
-            wgrad(dgt, transposed(h_prev), w_hh, b_hh, N)
-            if k > 0:
-                dh = torch.empty(N, H, **f)
-                ops.fc_dgrad(dg, self._transposed(f"ih{k}", w_ih), None, LINEAR, L.PREC_F32, dx32=dh)
+        dh0 = lstm_stack.backward(self.rnn, tape, dh_top, grad, tape["emb"], None, self._wt, want_dh0=True)
         demb = dh0[0]
         for k in range(1, self.num_hidden_layers):
             demb = demb + dh0[k]
-        wgrad(transposed(demb), transposed(tape["state0"]), self.map_linear.weight, self.map_linear.bias, B)
+        gw, gb = self.map_linear.weight, self.map_linear.bias
+        lstm_stack.wgrad(lstm_stack.transposed(demb), lstm_stack.transposed(tape["state0"]), grad[id(gw)], grad[id(gb)],
+                         tape["B"])
         return slab
