@@ -1444,6 +1444,50 @@ int rg_cem_refit(const double* rewards, const double* solutions, int population,
 int rg_cem_tally(const int* actions, int horizon, const double* rewards, int population, int action_dim, double* out,
                  rg_stream_t stream);
 
+/* Synthetic reward (reagent/models/synthetic_reward.py, reagent/training/reward_network_trainer.py).  Additive symbols: the
+ * ABI number does not move.  All fp32 unless said, on the caller's stream; no atomics, no flag a workgroup waits on: two runs
+ * give the same bits.
+ *
+ * rg_ngram_concat: ngram() over cat(state, action) (synthetic_reward.py:177-205, called at :399-403) in one launch.  state
+ * [T, B, S] and action [T, B, A] with row pitches ld_state / ld_action (elements between consecutive (t, b) rows), out
+ * [T, B, (S + A) * n] with row pitch ld_out, n = context_size odd.  For window slot i < n:
+ *   out[t, b, i * (S + A) + f] = cat(state, action)[t + i - n / 2, b, f]   when that step lies in [0, T), else 0.0f
+ * (the reference's ngram_padding is a zero tensor, not a parameter).  A pure copy: the inputs' bits.  n = 1 is the plain
+ * cat(state, action).  Total in n: a window wholly outside the sequence is zeros (the reference raises from narrow() when
+ * n / 2 > T).  RG_EINVAL for an even or non-positive n, a size below 1, a pitch below its row or a null pointer;
+ * RG_EUNSUPPORTED for T * B >= 2^29 or (S + A) * n >= 2^31.
+ *
+ * rg_step_reward_head: SyntheticRewardNet.forward behind the trunk (synthetic_reward.py:245-266) fused with the nets' last
+ * Linear(P, 1) + activation (:301-302, :389-390, :450-452) and _get_loss_function's wrapper
+ * (reward_network_trainer.py:27-66).  h [T, B, P] contiguous = the trunk's output, w [P], bias [1], act an RG_ACT_* code;
+ * valid_step [B] int64, CLAMPED into [1, T] inside the kernel (the reference's _gen_mask asserts the range on the host,
+ * :220-222); target [B]; loss_type an RG_SRW_LOSS_* code.
+ *   z[t, b] = h[t, b, :] . w + bias                (double; lanes stride over P, a fixed butterfly adds them)
+ *   r[t, b] = act(z);   mask[b, t] = (t >= T - v_b);   pred[b] = sum_t mask * r   (double, in t order, rounded once)
+ *   MSE (pred - target)^2; SmoothL1 with beta 1; L1; BCE: pred and target divided by v_b first, both logs clamped at -100 as
+ *   nn.BCELoss does, and a pred / v outside [0, 1] gives NaN for that row where torch raises.
+ *   kept[b] = !(has_threshold && apply_threshold) || fp32 target (BCE: target / v_b in fp32) <= (float)threshold: the
+ *   reference gates the filter on pred.requires_grad, so the caller sets apply_threshold in training and clears it in
+ *   validation.  loss = sum of the kept rows' losses / n_kept; with no row kept the loss is NaN and n_kept = 0 (the
+ *   reference asserts on the host), dh, dw and dbias zero.
+ * Outputs: output [B, T] (r transposed, as the reference returns it), mask [B, T], predicted_reward [B]; with target: loss
+ * [1], n_kept [1] int32; with dh: dh [T, B, P] = d loss / d h written entirely (+0 rows where the mask or the filter drops
+ * them), dw [P], dbias [1] from per-workgroup double partials added in a fixed order, every output rounded once.  The L1
+ * gradient at a zero residual is 0; BCE's is (p - y) / max(p (1 - p), 1e-12) / v, torch's.  target NULL: the three forward
+ * outputs alone (loss, n_kept, workspace may be NULL); dh NULL: no gradients (dw, dbias may be NULL).  The forward outputs
+ * have the same bits in every mode.  workspace: rg_step_reward_head_partials(B) * (P + 3) + (T + 1) * B doubles.  Three
+ * launches at most: the rows, the partials' sum (which makes n_kept), dh.
+ * RG_EINVAL for a size below 1, an act or loss_type outside its codes, a null pointer the mode needs; RG_EUNSUPPORTED for
+ * T * B >= 2^29. */
+enum { RG_SRW_LOSS_MSE = 0, RG_SRW_LOSS_SMOOTH_L1 = 1, RG_SRW_LOSS_L1 = 2, RG_SRW_LOSS_BCE = 3 };
+int rg_ngram_concat(const float* state, int64_t ld_state, const float* action, int64_t ld_action, int seq_len, int batch,
+                    int state_dim, int action_dim, int context_size, float* out, int64_t ld_out, rg_stream_t stream);
+int rg_step_reward_head_partials(int batch);
+int rg_step_reward_head(const float* h, const float* w, const float* bias, int act, const int64_t* valid_step,
+                        const float* target, int loss_type, int has_threshold, double threshold, int apply_threshold,
+                        int seq_len, int batch, int width, float* output, float* mask, float* predicted_reward, float* loss,
+                        int32_t* n_kept, float* dh, float* dw, float* dbias, double* workspace, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

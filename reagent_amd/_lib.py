@@ -31,6 +31,7 @@ MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's li
 STEP_CE_MAX_CLASSES = 32  # RG_STEP_CE_MAX_CLASSES: rg_step_ce_head's limit (Seq2Reward's multi_steps)
 CEM_MAX_MODELS, CEM_MAX_HORIZON, CEM_MAX_INPUT = 16, 64, 512  # RG_CEM_MAX_*: the CEM planner kernels' limits
 CEM_MAX_TRAJECTORIES = 1 << 20  # RG_CEM_MAX_TRAJECTORIES: population * ensemble stays below it
+SRW_LOSS = {"MSE_Loss": 0, "SmoothL1_Loss": 1, "L1_Loss": 2, "BCE_Loss": 3}  # RG_SRW_LOSS_*: rg_step_reward_head's losses under LossFunction's strings
 CB_LOSS = {"mse": 0, "mae": 1, "cross_entropy": 2}  # RG_CB_LOSS_*: rg_drlinucb_head's losses under the reference's LOSS_TYPES names
 
 c_void_p, c_int, c_i64, c_f, c_d, c_sz = (
@@ -365,6 +366,10 @@ SIGNATURES = {
     "rg_cem_sample_discrete": (c_int, [ctypes.c_uint64] + [c_int] * 4 + [c_void_p, c_void_p]),
     "rg_cem_refit": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_d, c_d, c_void_p, c_void_p, c_void_p]),
     "rg_cem_tally": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "rg_ngram_concat": (c_int, [c_void_p, c_i64, c_void_p, c_i64] + [c_int] * 5 + [c_void_p, c_i64, c_void_p]),
+    "rg_step_reward_head_partials": (c_int, [c_int]),
+    "rg_step_reward_head": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_d, c_int] + [c_int] * 3
+                            + [c_void_p] * 9 + [c_void_p]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), SyntheticRewardNetworkOutput, CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -450,6 +450,15 @@ class Seq2RewardOutput(TensorDataClass):
     acc_reward: torch.Tensor
 
 
+@dataclass
+class SyntheticRewardNetworkOutput(TensorDataClass):
+    """:1098-1102 — the synthetic-reward nets' output: predicted_reward [B, 1], mask [B, seq_len], output [B, seq_len]"""
+
+    predicted_reward: torch.Tensor
+    mask: torch.Tensor
+    output: torch.Tensor
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -472,7 +481,7 @@ _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
                   "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput", "MemoryNetworkInput",
-                  "MemoryNetworkOutput", "Seq2RewardOutput"):
+                  "MemoryNetworkOutput", "Seq2RewardOutput", "SyntheticRewardNetworkOutput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

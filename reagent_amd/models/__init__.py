@@ -13,3 +13,9 @@ from .categorical_dqn import CategoricalDQN  # noqa: F401
 from .linear_regression import LinearRegressionUCB  # noqa: F401
 from .deep_represent_linucb import DeepRepresentLinearRegressionUCB  # noqa: F401
 from .disjoint_linucb_predictor import DisjointLinearRegressionUCB  # noqa: F401
+from .synthetic_reward import (  # noqa: F401
+    NGramFullyConnectedNetwork,
+    SequenceSyntheticRewardNet,
+    SingleStepSyntheticRewardNet,
+    SyntheticRewardNet,
+)

@@ -1777,3 +1777,61 @@ def dueling_split(dq, num_actions, num_atoms, dadv, dvalue):
     _run("rg_dueling_split", dict(B=B, A=num_actions, N=num_atoms),
          lambda: L.lib().rg_dueling_split(dq.data_ptr(), _ld(dq), B, num_actions, num_atoms, dadv.data_ptr(), _ld(dadv),
                                           dvalue.data_ptr(), _ld(dvalue), L.stream_ptr()))
+
+
+# ---- synthetic reward --------------------------------------------------------------------------------------------------
+def ngram_concat(state, action, context_size: int, out):
+    """out [T, B, (S + A) * n] = ngram(cat(state, action), n) (see rg_ngram_concat): window slot i of step t holds step
+    t + i - n // 2, zeros outside the sequence; n = 1 is the plain cat.  state [T, B, S], action [T, B, A] and out may have
+    padded rows (a unit last stride and (t, b) rows a constant pitch apart)"""
+    _chk_dev(state, action, out)
+    T, B, S = state.shape
+    A, n = action.shape[2], int(context_size)
+    if n < 1 or n % 2 == 0:
+        raise NotImplementedError(f"ngram_concat: context_size {n} is not supported (odd, at least 1)")
+    if T * B >= 1 << 29:
+        raise NotImplementedError(f"ngram_concat: seq_len * batch = {T * B} is not supported (below 2^29)")
+    assert action.shape[:2] == (T, B) and out.shape == (T, B, (S + A) * n)
+    for t in (state, action, out):
+        assert t.dtype == F32 and t.stride(2) == 1 and (B == 1 or t.stride(0) == B * t.stride(1)), "rows a constant pitch apart"
+    ld = lambda t: t.stride(1) if B > 1 or T == 1 else t.stride(0)  # noqa: E731
+    _run("rg_ngram_concat", dict(T=T, B=B, S=S, A=A, n=n),
+         lambda: L.lib().rg_ngram_concat(L.ptr(state), ld(state), L.ptr(action), ld(action), T, B, S, A, n, L.ptr(out), ld(out),
+                                         L.stream_ptr()))
+
+
+def step_reward_head_partials(batch: int) -> int:
+    return int(L.lib().rg_step_reward_head_partials(batch))
+
+
+def step_reward_head_workspace(seq_len: int, batch: int, width: int) -> int:
+    """doubles of workspace rg_step_reward_head asks for"""
+    return step_reward_head_partials(batch) * (width + 3) + (seq_len + 1) * batch
+
+
+def step_reward_head(h, w, bias, act: int, valid_step, output, mask, predicted_reward, target=None, loss_type: int = 0,
+                     threshold=None, apply_threshold: bool = False, loss=None, n_kept=None, dh=None, dw=None, dbias=None,
+                     workspace=None):
+    """the synthetic-reward head behind the trunk's output h [T, B, P] (see rg_step_reward_head): the last Linear(P, 1) and
+    its activation, the valid-step mask and the masked sum; with target [B] the loss (threshold=None: no filter) and n_kept;
+    with dh the gradients.  valid_step [B] int64 is clamped into [1, T] by the kernel"""
+    _chk_dev(h, w, bias, valid_step, output, mask, predicted_reward, target, loss, n_kept, dh, dw, dbias, workspace)
+    T, B, P = h.shape
+    if T * B >= 1 << 29:
+        raise NotImplementedError(f"step_reward_head: seq_len * batch = {T * B} is not supported (below 2^29)")
+    _f32_flat(h, T * B * P), _f32_flat(w, P), _f32_flat(bias, 1), _f32_flat(output, B * T), _f32_flat(mask, B * T)
+    _f32_flat(predicted_reward, B), _f32_flat(target, B), _f32_flat(loss, 1), _f32_flat(dh, T * B * P), _f32_flat(dw, P)
+    _f32_flat(dbias, 1)
+    assert valid_step.dtype == torch.int64 and valid_step.is_contiguous() and valid_step.numel() == B
+    if target is not None:
+        assert loss is not None and n_kept is not None and n_kept.dtype == torch.int32 and n_kept.numel() == 1
+        assert workspace.dtype == torch.float64 and workspace.is_contiguous()
+        assert workspace.numel() >= step_reward_head_workspace(T, B, P)
+    if dh is not None:
+        assert target is not None and dw is not None and dbias is not None
+    _run("rg_step_reward_head", dict(T=T, B=B, P=P, train=dh is not None),
+         lambda: L.lib().rg_step_reward_head(L.ptr(h), L.ptr(w), L.ptr(bias), int(act), L.ptr(valid_step), L.ptr(target),
+                                             int(loss_type), int(threshold is not None),
+                                             float(threshold) if threshold is not None else 0.0, int(bool(apply_threshold)), T, B,
+                                             P, L.ptr(output), L.ptr(mask), L.ptr(predicted_reward), L.ptr(loss), L.ptr(n_kept),
+                                             L.ptr(dh), L.ptr(dw), L.ptr(dbias), L.ptr(workspace), L.stream_ptr()))

@@ -239,6 +239,47 @@ def to_seq2reward_input(d: Dict[str, torch.Tensor], device=None):
     return b
 
 
+def synthetic_reward_batch(seq_len: int, batch: int, state_dim: int, action_dim: int, seed: int = 0, binary_reward: bool = False,
+                           sequence: bool = False) -> Dict[str, torch.Tensor]:
+    """A batch for the synthetic-reward nets, as create_data / create_sequence_data of the reference's
+    test_synthetic_reward_training.py make theirs: state and action 2 * randn [T, B, .], valid_step [B, 1] int64 in 1 ..
+    seq_len (both ends occur once the batch allows), and reward [B, 1] = the sum over each row's last valid_step steps of a
+    per-step reward that is a fixed linear function (weights from seed 0 of the shape: every batch has the same task) of
+    cat(state, action) (its sigmoid with binary_reward) or, with sequence, of the masked features of the steps before and
+    after"""
+    T, B, S, A, scale = seq_len, batch, state_dim, action_dim, 2
+    weight = scale * torch.randn(S + A, generator=torch.Generator().manual_seed(1000 * S + A))
+    g = torch.Generator().manual_seed(seed)
+    state = scale * torch.randn(T, B, S, generator=g)
+    action = scale * torch.randn(T, B, A, generator=g)
+    valid_step = torch.randint(1, T + 1, (B, 1), generator=g)
+    if B >= 2:
+        valid_step[0, 0], valid_step[-1, 0] = 1, T
+    mask = (torch.arange(T).repeat(B, 1) >= (T - valid_step)).float()  # [B, T]
+    feature = torch.cat((state, action), dim=2)
+    if sequence:
+        masked = feature * mask.transpose(0, 1).unsqueeze(-1)
+        zero = torch.zeros(1, B, S + A)
+        feature = torch.cat((masked[1:], zero), dim=0) + torch.cat((zero, masked[:-1]), dim=0)
+    reward_matrix = torch.matmul(feature, weight).transpose(0, 1)
+    if binary_reward:
+        reward_matrix = torch.sigmoid(reward_matrix)
+    reward = (reward_matrix * mask).sum(dim=1).reshape(-1, 1)
+    return dict(state=state, action=action, valid_step=valid_step, reward=reward.contiguous())
+
+
+def to_synthetic_reward_input(d: Dict[str, torch.Tensor], device=None):
+    """MemoryNetworkInput with valid_step and reward [B, 1]; the fields the reward trainer does not read are empty, as in the
+    reference's test data"""
+    from .core import types as rlt
+
+    t = (lambda x: x.to(device)) if device is not None else (lambda x: x)
+    empty = torch.tensor([])
+    return rlt.MemoryNetworkInput(state=rlt.FeatureData(t(d["state"])), action=rlt.FeatureData(t(d["action"])),
+                                  valid_step=t(d["valid_step"]), reward=t(d["reward"]), next_state=empty, step=empty,
+                                  not_terminal=empty, time_diff=empty)
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 

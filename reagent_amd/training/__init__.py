@@ -10,6 +10,7 @@ from .slate_q_trainer import NextSlateValueNormMethod, SlateQTrainer  # noqa: F4
 from .reinforce_trainer import ReinforceTrainer  # noqa: F401
 from .ppo_trainer import PPOTrainer  # noqa: F401
 from .cem_trainer import CEMTrainer  # noqa: F401
+from .reward_network_trainer import LossFunction, RewardNetTrainer  # noqa: F401
 from .cb import DeepRepresentLinUCBTrainer, DisjointLinUCBTrainer, LinUCBTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
@@ -19,6 +20,7 @@ from .parameters import (  # noqa: F401
     PPOTrainerParameters,
     QRDQNTrainerParameters,
     ReinforceTrainerParameters,
+    RewardNetworkTrainerParameters,
     SACTrainerParameters,
     SlateQTrainerParameters,
     TD3TrainerParameters,

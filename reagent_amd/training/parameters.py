@@ -22,6 +22,7 @@ from .parametric_dqn_trainer import ParametricDQNTrainer
 from .ppo_trainer import PPOTrainer
 from .qrdqn_trainer import QRDQNTrainer
 from .reinforce_trainer import ReinforceTrainer
+from .reward_network_trainer import RewardNetTrainer
 from .sac_trainer import SACTrainer
 from .slate_q_trainer import SlateQTrainer
 from .td3_trainer import TD3Trainer
@@ -128,3 +129,8 @@ class ReinforceTrainerParameters:
 @make_config_class(PPOTrainer.__init__, blocklist=["policy", "value_net"])
 class PPOTrainerParameters:
     """parameters.py:142-150"""
+
+
+@make_config_class(RewardNetTrainer.__init__, blocklist=["reward_net"])
+class RewardNetworkTrainerParameters:
+    """parameters.py:131-133"""
