@@ -1488,6 +1488,94 @@ int rg_step_reward_head(const float* h, const float* w, const float* bias, int a
                         int seq_len, int batch, int width, float* output, float* mask, float* predicted_reward, float* loss,
                         int32_t* n_kept, float* dh, float* dw, float* dbias, double* workspace, rg_stream_t stream);
 
+/* Counterfactual-evaluation reward models (reagent/training/cfeval/, reagent/models/probabilistic_fully_connected_network.py).
+ * Additive symbols: the ABI number does not move.  All fp32 unless said, on the caller's stream; no atomics, no flag a
+ * workgroup waits on; per-workgroup partials in double, added in a fixed order by a finishing launch; every output rounded
+ * once; two runs give the same bits.
+ *
+ * The Bayes-by-backprop kernels walk a SEGMENT TABLE: up to RG_BBB_MAX_SEGMENTS flat parameter tensors (a layer's weights and
+ * its biases are a segment each, so eight layers), passed by value, so the number of launches does not depend on depth.  A
+ * workgroup takes RG_BBB_CHUNK consecutive elements of one segment.
+ *
+ * rg_bbb_sample: LinearBBB.forward's weight draw and both log-densities (probabilistic_fully_connected_network.py:87-105)
+ * for every segment, and log_prior() / log_post() (:175-188) over them.  Per element, in double on the fp32 inputs:
+ *   sigma = log(1 + exp(rho))   (as rho + log1p(exp(-rho)) for rho > 0, log1p(exp(rho)) otherwise: finite and positive for
+ *                                every rho in [-700, 3e38], where the reference's fp32 form is inf above 88 and 0 below -17)
+ *   w     = fp32(mu + sigma * eps)
+ *   log_prior += log Normal(0, prior_var).pdf(w)      (the ROUNDED w; prior_var is the prior's SCALE: the reference's quirk)
+ *   log_post  += log Normal(mu, sigma).pdf(w)
+ * eps: with draw = 0 read from seg.eps (the explicit-noise path); with draw = 1 drawn and written to seg.eps:
+ * Philox4x32-10 (rg_philox.h) with key = seed, counter words (c0, c1) = the element's index in its segment (low, high),
+ * c2 = the sample index, c3 = the segment's index in the table; the first two output words make u1 = (x0 + 1) / 2^32 in
+ * (0, 1] and u2 = x1 / 2^32 in [0, 1), eps = fp32(sqrt(-2 ln u1) cos(2 pi u2)) with the arithmetic in double.
+ * rg_bbb_fill_noise writes exactly that eps and nothing else.  Outputs: seg.w, seg.eps (draw), log_prior [1], log_post [1]
+ * (fp32, rounded once) and terms[0] = log_prior, terms[1] = log_post as doubles for rg_bbb_elbo_head.  workspace:
+ * 2 * rg_bbb_chunks(table) doubles.  Two launches.
+ *
+ * rg_bbb_elbo_head: sample_elbo's likelihood and loss (:190-213) for one sample.  out [B] (the network's one output column,
+ * pitch ld_out), target [B]:
+ *   log_like = sum_r log Normal(out_r, noise_tol).pdf(target_r)           (double per row, fixed order)
+ *   acc      = (accumulate ? acc : 0) + scale * (log_post - log_prior - log_like, log_prior, log_post, log_like)
+ *   result[0 .. 3] = fp32(acc)      (the loss and its three terms; scale = 1 / num_samples, accumulate on every sample but
+ *                                    the first: the Monte-Carlo means of :205-210)
+ *   dout_r   = scale * (out_r - target_r) / noise_tol^2                   (d loss / d out; may be NULL)
+ * terms: rg_bbb_sample's two doubles; acc: 4 doubles the caller keeps between samples; workspace:
+ * rg_bbb_elbo_head_partials(B) doubles.  Two launches.
+ *
+ * rg_bbb_grad: autograd's chain rule back into mu and rho (one launch), after the network's backward left
+ * seg.dw = d (-log_like) / d w (times the head's scale).  Per element, in double:
+ *   g     = dw + scale * (w / prior_var^2 - (w - mu) / sigma^2)
+ *   dmu   = g                       (the posterior's mean is w_mu.data: detached in the reference, :101-102, kept)
+ *   drho  = sigmoid(rho) * (g * eps + scale * ((w - mu)^2 / sigma^3 - 1 / sigma))
+ * written to seg.dmu / seg.drho, added to them with accumulate (the host loop over num_samples).
+ *
+ * rg_bandit_reward_head: BanditRewardNetTrainer behind the [B, A] forward (cfeval/bandit_reward_network_trainer.py:57-61,
+ * :48-55, :63-75 and the loss wrapper of reward_network_trainer.py:27-66).  q [B, A] (pitch ld_q), action [B, A] (pitch
+ * ld_action), reward [B], action_prob [B] or NULL:
+ *   idx_r  = argmax(action[r, :]) by torch.argmax's rule: the first maximum, a NaN ranking above everything
+ *   pred_r = q[r, idx_r];  l_r = MSE, SmoothL1 (beta 1) or L1 of (pred_r, reward_r)  (RG_SRW_LOSS_* codes; BCE: RG_EINVAL)
+ *   weight_r = 1 / action_prob_r (1 without action_prob)
+ *   kept_r = !(has_threshold && apply_threshold) || reward_r <= (float)threshold
+ *   loss = sum_kept weight_r l_r / n_kept;  unweighted_loss = sum_kept l_r / n_kept;  n_kept int32
+ *   dq[r, c] = weight_r * dl_r / n_kept at c = idx_r of a kept row, +0 everywhere else (written whole; may be NULL)
+ * With no row kept the losses are NaN, n_kept = 0 and dq zero (rg_step_reward_head's convention).  The L1 gradient at a
+ * zero residual is 0.  predicted_reward [B] is always written.  workspace: rg_bandit_reward_head_workspace(B) doubles.  Two
+ * launches: the rows, then the partials' sum in every workgroup (the same order: the same bits) and dq.
+ *
+ * RG_EINVAL for a null pointer a mode needs, a size below 1, more than RG_BBB_MAX_SEGMENTS segments, a non-positive
+ * prior_var or noise_tol, a loss code outside MSE / SmoothL1 / L1; RG_EUNSUPPORTED for a segment of 2^31 elements or more. */
+#define RG_BBB_MAX_SEGMENTS 16
+#define RG_BBB_CHUNK 1024
+typedef struct rg_bbb_segment {
+  const float* mu;
+  const float* rho;
+  float* w;        /* the sampled tensor: written by rg_bbb_sample, read by rg_bbb_grad */
+  float* eps;      /* the noise: read (draw = 0) or written (draw = 1) by rg_bbb_sample, read by rg_bbb_grad */
+  const float* dw; /* rg_bbb_grad: d (-log_like) / d w */
+  float* dmu;      /* rg_bbb_grad's outputs */
+  float* drho;
+  int64_t n;
+} rg_bbb_segment;
+typedef struct rg_bbb_table {
+  int32_t n_segments;
+  int32_t reserved;
+  rg_bbb_segment seg[RG_BBB_MAX_SEGMENTS];
+} rg_bbb_table;
+int rg_bbb_chunks(const rg_bbb_table* table);
+int rg_bbb_fill_noise(const rg_bbb_table* table, uint64_t seed, int sample, rg_stream_t stream);
+int rg_bbb_sample(const rg_bbb_table* table, double prior_var, int draw, uint64_t seed, int sample, float* log_prior,
+                  float* log_post, double* terms, double* workspace, rg_stream_t stream);
+int rg_bbb_elbo_head_partials(int batch);
+int rg_bbb_elbo_head(const float* out, int64_t ld_out, const float* target, int batch, double noise_tol, double scale,
+                     int accumulate, const double* terms, double* acc, float* result, float* dout, double* workspace,
+                     rg_stream_t stream);
+int rg_bbb_grad(const rg_bbb_table* table, double prior_var, double scale, int accumulate, rg_stream_t stream);
+int rg_bandit_reward_head_workspace(int batch);
+int rg_bandit_reward_head(const float* q, int64_t ld_q, const float* action, int64_t ld_action, const float* reward,
+                          const float* action_prob, int loss_type, int has_threshold, double threshold, int apply_threshold,
+                          int batch, int num_actions, float* predicted_reward, float* loss, float* unweighted_loss,
+                          int32_t* n_kept, float* dq, int64_t ld_dq, double* workspace, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,18 @@ class NormCol(ctypes.Structure):
     ]
 
 
+BBB_MAX_SEGMENTS, BBB_CHUNK = 16, 1024  # RG_BBB_MAX_SEGMENTS, RG_BBB_CHUNK
+
+
+class BbbSegment(ctypes.Structure):
+    _fields_ = [("mu", c_void_p), ("rho", c_void_p), ("w", c_void_p), ("eps", c_void_p), ("dw", c_void_p), ("dmu", c_void_p),
+                ("drho", c_void_p), ("n", c_i64)]
+
+
+class BbbTable(ctypes.Structure):
+    _fields_ = [("n_segments", ctypes.c_int32), ("reserved", ctypes.c_int32), ("seg", BbbSegment * BBB_MAX_SEGMENTS)]
+
+
 MLP_MAX_LAYERS = 6
 
 
@@ -370,6 +382,15 @@ SIGNATURES = {
     "rg_step_reward_head_partials": (c_int, [c_int]),
     "rg_step_reward_head": (c_int, [c_void_p] * 3 + [c_int, c_void_p, c_void_p, c_int, c_int, c_d, c_int] + [c_int] * 3
                             + [c_void_p] * 9 + [c_void_p]),
+    "rg_bbb_chunks": (c_int, [c_void_p]),
+    "rg_bbb_fill_noise": (c_int, [c_void_p, ctypes.c_uint64, c_int, c_void_p]),
+    "rg_bbb_sample": (c_int, [c_void_p, c_d, c_int, ctypes.c_uint64, c_int] + [c_void_p] * 4 + [c_void_p]),
+    "rg_bbb_elbo_head_partials": (c_int, [c_int]),
+    "rg_bbb_elbo_head": (c_int, [c_void_p, c_i64, c_void_p, c_int, c_d, c_d, c_int] + [c_void_p] * 5 + [c_void_p]),
+    "rg_bbb_grad": (c_int, [c_void_p, c_d, c_d, c_int, c_void_p]),
+    "rg_bandit_reward_head_workspace": (c_int, [c_int]),
+    "rg_bandit_reward_head": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_int, c_int, c_d, c_int, c_int, c_int]
+                              + [c_void_p] * 5 + [c_i64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), SyntheticRewardNetworkOutput, CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), SyntheticRewardNetworkOutput, BanditRewardModelInput (:977-995), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -459,6 +459,30 @@ class SyntheticRewardNetworkOutput(TensorDataClass):
     output: torch.Tensor
 
 
+@dataclass
+class BanditRewardModelInput(TensorDataClass):
+    """:977-995 — logged bandit data: state, the logged action [B, A] (one-hot), reward [B, 1] and, for the inverse
+    propensity weighting, the logging policy's probability of that action [B, 1]"""
+
+    state: FeatureData
+    action: torch.Tensor
+    reward: torch.Tensor
+    action_prob: Optional[torch.Tensor] = None
+
+    @classmethod
+    def from_dict(cls, batch):
+        return cls(
+            state=FeatureData(float_features=batch["state_features"]),
+            action=batch["action"],
+            reward=batch["reward"],
+            action_prob=batch.get("action_probability", None),
+        )
+
+    def batch_size(self):
+        assert self.state.float_features.ndim == 2
+        return self.state.float_features.size()[0]
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -481,7 +505,7 @@ _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
                   "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput", "MemoryNetworkInput",
-                  "MemoryNetworkOutput", "Seq2RewardOutput", "SyntheticRewardNetworkOutput"):
+                  "MemoryNetworkOutput", "Seq2RewardOutput", "SyntheticRewardNetworkOutput", "BanditRewardModelInput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

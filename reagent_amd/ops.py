@@ -1835,3 +1835,99 @@ def step_reward_head(h, w, bias, act: int, valid_step, output, mask, predicted_r
                                              float(threshold) if threshold is not None else 0.0, int(bool(apply_threshold)), T, B,
                                              P, L.ptr(output), L.ptr(mask), L.ptr(predicted_reward), L.ptr(loss), L.ptr(n_kept),
                                              L.ptr(dh), L.ptr(dw), L.ptr(dbias), L.ptr(workspace), L.stream_ptr()))
+
+
+# ---- counterfactual-evaluation reward models (bbb.hip) -----------------------------------------------------------------
+def bbb_table(segments) -> "L.BbbTable":
+    """the segment table of the Bayes-by-backprop kernels (see rg_bbb_sample) from dicts of flat fp32 tensors: mu, rho, w,
+    eps and, for rg_bbb_grad, dw, dmu, drho.  The caller keeps the tensors alive while the table is in use."""
+    if not 1 <= len(segments) <= L.BBB_MAX_SEGMENTS:
+        raise NotImplementedError(f"bbb_table: {len(segments)} segments are not supported (1 to {L.BBB_MAX_SEGMENTS}: a layer's "
+                                  "weights and its biases are a segment each)")
+    t = L.BbbTable()
+    t.n_segments = len(segments)
+    for i, s in enumerate(segments):
+        n = s["mu"].numel()
+        for k in ("mu", "rho", "w", "eps", "dw", "dmu", "drho"):
+            v = s.get(k)
+            if v is not None:
+                _chk_dev(v)
+                assert v.dtype == F32 and v.is_contiguous() and v.numel() == n, (i, k, v.shape, v.dtype)
+            setattr(t.seg[i], k, L.ptr(v))
+        t.seg[i].n = n
+    return t
+
+
+def bbb_chunks(table) -> int:
+    return int(L.lib().rg_bbb_chunks(ctypes.byref(table)))
+
+
+def bbb_fill_noise(table, seed: int, sample: int = 0):
+    """every segment's eps = what rg_bbb_sample would draw in place for (seed, sample)"""
+    _run("rg_bbb_fill_noise", dict(chunks=bbb_chunks(table)),
+         lambda: L.lib().rg_bbb_fill_noise(ctypes.byref(table), int(seed), int(sample), L.stream_ptr()))
+
+
+def bbb_sample(table, prior_var: float, log_prior, log_post, terms, workspace, seed: Optional[int] = None, sample: int = 0):
+    """w = mu + softplus(rho) * eps for every segment and the two log-densities (see rg_bbb_sample); seed None: eps is read
+    (the explicit-noise path), else drawn and written.  terms: 2 doubles for bbb_elbo_head."""
+    _chk_dev(log_prior, log_post, terms, workspace)
+    chunks = bbb_chunks(table)
+    assert terms.dtype == workspace.dtype == torch.float64 and terms.numel() >= 2 and workspace.numel() >= 2 * chunks
+    assert log_prior.dtype == log_post.dtype == F32
+    _run("rg_bbb_sample", dict(chunks=chunks, draw=seed is not None),
+         lambda: L.lib().rg_bbb_sample(ctypes.byref(table), float(prior_var), int(seed is not None), int(seed or 0), int(sample),
+                                       L.ptr(log_prior), L.ptr(log_post), L.ptr(terms), L.ptr(workspace), L.stream_ptr()))
+
+
+def bbb_elbo_head_partials(batch: int) -> int:
+    return int(L.lib().rg_bbb_elbo_head_partials(batch))
+
+
+def bbb_elbo_head(out, target, noise_tol: float, terms, acc, result, workspace, dout=None, scale: float = 1.0,
+                  accumulate: bool = False):
+    """the ELBO's likelihood, the loss and d loss / d out for one sample (see rg_bbb_elbo_head): out [B, 1] or [B], target
+    [B]; result [4] = the loss, log_prior, log_post, log_like (means over the samples so far)"""
+    _chk_dev(out, target, terms, acc, result, workspace, dout)
+    B = target.numel()
+    ld = out.stride(0) if out.dim() == 2 else 1
+    assert out.shape[0] == B and out.numel() == B and out.dtype == target.dtype == result.dtype == F32 and target.is_contiguous()
+    assert acc.dtype == torch.float64 and acc.numel() >= 4 and result.numel() >= 4
+    assert workspace.dtype == torch.float64 and workspace.numel() >= bbb_elbo_head_partials(B)
+    assert dout is None or (dout.dtype == F32 and dout.is_contiguous() and dout.numel() == B)
+    _run("rg_bbb_elbo_head", dict(B=B),
+         lambda: L.lib().rg_bbb_elbo_head(L.ptr(out), ld, L.ptr(target), B, float(noise_tol), float(scale), int(accumulate),
+                                          L.ptr(terms), L.ptr(acc), L.ptr(result), L.ptr(dout), L.ptr(workspace), L.stream_ptr()))
+
+
+def bbb_grad(table, prior_var: float, scale: float = 1.0, accumulate: bool = False):
+    """d loss / d mu and d loss / d rho of every segment from its dw = d (-log_like) / d w (see rg_bbb_grad)"""
+    _run("rg_bbb_grad", dict(chunks=bbb_chunks(table)),
+         lambda: L.lib().rg_bbb_grad(ctypes.byref(table), float(prior_var), float(scale), int(accumulate), L.stream_ptr()))
+
+
+def bandit_reward_head_workspace(batch: int) -> int:
+    """doubles of workspace rg_bandit_reward_head asks for"""
+    return int(L.lib().rg_bandit_reward_head_workspace(batch))
+
+
+def bandit_reward_head(q, action, reward, predicted_reward, loss, n_kept, workspace, action_prob=None, loss_type: int = 0,
+                       threshold: Optional[float] = None, apply_threshold: bool = True, unweighted_loss=None, dq=None):
+    """the bandit reward trainer behind its [B, A] forward (see rg_bandit_reward_head): the logged action's prediction, the
+    loss over the kept rows (weighted by 1 / action_prob when given), the unweighted loss, n_kept and d loss / d q"""
+    _chk_dev(q, action, reward, predicted_reward, loss, n_kept, workspace, action_prob, unweighted_loss, dq)
+    B, A = q.shape
+    if B * A >= 1 << 31:
+        raise NotImplementedError(f"bandit_reward_head: batch * actions = {B * A} is not supported (below 2^31)")
+    assert action.shape == (B, A) and q.dtype == action.dtype == reward.dtype == F32
+    assert reward.numel() == B and reward.is_contiguous() and predicted_reward.numel() == B and predicted_reward.is_contiguous()
+    assert action_prob is None or (action_prob.dtype == F32 and action_prob.numel() == B and action_prob.is_contiguous())
+    assert n_kept.dtype == torch.int32 and workspace.dtype == torch.float64
+    assert workspace.numel() >= bandit_reward_head_workspace(B)
+    assert dq is None or (dq.shape == (B, A) and dq.dtype == F32)
+    _run("rg_bandit_reward_head", dict(B=B, A=A, train=dq is not None),
+         lambda: L.lib().rg_bandit_reward_head(L.ptr(q), _ld(q), L.ptr(action), _ld(action), L.ptr(reward), L.ptr(action_prob),
+                                               int(loss_type), int(threshold is not None),
+                                               float(threshold) if threshold is not None else 0.0, int(apply_threshold), B, A,
+                                               L.ptr(predicted_reward), L.ptr(loss), L.ptr(unweighted_loss), L.ptr(n_kept),
+                                               L.ptr(dq), _ld(dq) if dq is not None else 0, L.ptr(workspace), L.stream_ptr()))

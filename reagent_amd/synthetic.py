@@ -280,6 +280,26 @@ def to_synthetic_reward_input(d: Dict[str, torch.Tensor], device=None):
                                   not_terminal=empty, time_diff=empty)
 
 
+def bandit_reward_batch(batch: int, state_dim: int, num_actions: int, seed: int = 0, with_propensities: bool = False,
+                        device=None):
+    """A seeded rlt.BanditRewardModelInput of logged bandit data: state randn [B, S], a uniformly logged one-hot action [B, A],
+    reward [B, 1] = a fixed linear function of the state per action (weights from the shape: every batch has the same task)
+    plus 0.1 randn and, with_propensities, action_prob [B, 1] in (0, 1]"""
+    from .core import types as rlt
+
+    B, S, A = batch, state_dim, num_actions
+    weight = torch.randn(A, S, generator=torch.Generator().manual_seed(1000 * S + A))
+    g = torch.Generator().manual_seed(seed)
+    state = torch.randn(B, S, generator=g)
+    idx = torch.randint(0, A, (B,), generator=g)
+    action = torch.nn.functional.one_hot(idx, A).float()
+    reward = ((state @ weight.t()).gather(1, idx.view(B, 1)) + 0.1 * torch.randn(B, 1, generator=g)).contiguous()
+    prob = (1.0 - 0.9 * torch.rand(B, 1, generator=g)) if with_propensities else None
+    t = (lambda x: x.to(device)) if device is not None else (lambda x: x)
+    return rlt.BanditRewardModelInput(state=rlt.FeatureData(t(state)), action=t(action), reward=t(reward),
+                                      action_prob=t(prob) if prob is not None else None)
+
+
 def to_dqn_input(d: Dict[str, torch.Tensor], device=None):
     from .core import types as rlt
 

@@ -11,6 +11,7 @@ from .reinforce_trainer import ReinforceTrainer  # noqa: F401
 from .ppo_trainer import PPOTrainer  # noqa: F401
 from .cem_trainer import CEMTrainer  # noqa: F401
 from .reward_network_trainer import LossFunction, RewardNetTrainer  # noqa: F401
+from .cfeval import BanditRewardNetTrainer  # noqa: F401
 from .cb import DeepRepresentLinUCBTrainer, DisjointLinUCBTrainer, LinUCBTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
