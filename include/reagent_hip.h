@@ -1576,6 +1576,38 @@ int rg_bandit_reward_head(const float* q, int64_t ld_q, const float* action, int
                           int batch, int num_actions, float* predicted_reward, float* loss, float* unweighted_loss,
                           int32_t* n_kept, float* dq, int64_t ld_dq, double* workspace, rg_stream_t stream);
 
+/* ---- multi-head self-attention over short sequences (attention.hip) ----------------------------------------------------
+ * nn.MultiheadAttention's core between its projections, with no mask, as PETransformerEncoderLayer calls it
+ * (reagent/models/synthetic_reward.py:160-166).  q, k, v, ctx and the gradients are fp32 [seq_len * batch, embed] views, row
+ * t * batch + b, each with its own pitch (q | k and dq | dk may be the halves of one [N, 2 * embed] buffer); head h owns
+ * columns h * hd .. (h + 1) * hd, hd = embed / nhead.
+ *
+ * rg_attn_forward: ctx = softmax(q k^T / sqrt(hd)) v per (b, head); p (nullable) [batch, nhead, seq_len, seq_len] contiguous =
+ * the probabilities, which the backward reads.  Dot products and the soft-max (row maximum subtracted) in double on the fp32
+ * inputs, p and ctx rounded once; a wave owns a (b, head) pair, nothing is added across waves, no atomics: two runs give the
+ * same bits.  rg_attn_backward: dv = p^T dctx, dp = dctx v^T, ds = p * (dp - rowsum(dp * p)), dq = ds k / sqrt(hd),
+ * dk = ds^T q / sqrt(hd), every output written entirely and rounded once.
+ * RG_EINVAL for embed % nhead != 0, a pitch below embed or a missing pointer; RG_EUNSUPPORTED for seq_len >
+ * RG_ATTN_MAX_SEQ_LEN (a score row is one wavefront, a lane per key), embed / nhead > RG_ATTN_MAX_HEAD_DIM, embed >
+ * RG_ATTN_MAX_EMBED, seq_len * batch >= 2^29 or batch * nhead >= 2^29. */
+#define RG_ATTN_MAX_SEQ_LEN 64
+#define RG_ATTN_MAX_HEAD_DIM 128
+#define RG_ATTN_MAX_EMBED 512
+int rg_attn_forward(const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v, int64_t ldv, int seq_len, int batch,
+                    int embed, int nhead, float* ctx, int64_t ld_ctx, float* p, rg_stream_t stream);
+int rg_attn_backward(const float* dctx, int64_t ld_dctx, const float* q, int64_t ldq, const float* k, int64_t ldk, const float* v,
+                     int64_t ldv, const float* p, int seq_len, int batch, int embed, int nhead, float* dq, int64_t ld_dq,
+                     float* dk, int64_t ld_dk, float* dv, int64_t ld_dv, rg_stream_t stream);
+/* out = act((a + b) + pe[row / batch]) on strided fp32 [seq_len * batch, cols] views in one launch: b and pe [>= seq_len,
+ * cols] (pitch ld_pe) nullable, act RG_ACT_LINEAR or RG_ACT_RELU; each element is fp32 adds in that order.
+ * rg_residual_join_backward: dx = (((g0 + g1) + g2) + g3) where out > 0 (out: the join's saved relu output, nullable: no
+ * mask; g1 .. g3 nullable), 0 elsewhere, a NaN in out passing the sum. */
+int rg_residual_join(const float* a, int64_t lda, const float* b, int64_t ldb, const float* pe, int64_t ld_pe, int seq_len,
+                     int batch, int cols, int act, float* out, int64_t ldo, rg_stream_t stream);
+int rg_residual_join_backward(const float* out, int64_t ldo, const float* g0, int64_t ld0, const float* g1, int64_t ld1,
+                              const float* g2, int64_t ld2, const float* g3, int64_t ld3, int64_t rows, int cols, float* dx,
+                              int64_t ld_dx, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

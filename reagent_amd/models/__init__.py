@@ -19,3 +19,4 @@ from .synthetic_reward import (  # noqa: F401
     SingleStepSyntheticRewardNet,
     SyntheticRewardNet,
 )
+from .synthetic_reward_transformer import TransformerSyntheticRewardNet  # noqa: F401

@@ -23,7 +23,8 @@ _gen_mask asserts on the host.
 
 Refused by name: lstm_bidirectional, lstm_hidden_size > 256, lstm_num_layers > 4 (the LSTM kernels' limits), an even
 context_size, an activation outside the six HIP epilogues, use_batch_norm on the single-step net (its BatchNorm1d would see
-3-D input).  Not built: NGramConvolutionalNetwork and TransformerSyntheticRewardNet.
+3-D input).  TransformerSyntheticRewardNet is its own module, models/synthetic_reward_transformer.py (re-exported from
+reagent_amd.models, not from here).  Not built: NGramConvolutionalNetwork.
 
 ngram and _gen_mask are plain torch statements of the reference's functions: the tests compare the kernels against them.
 """

@@ -1931,3 +1931,81 @@ def bandit_reward_head(q, action, reward, predicted_reward, loss, n_kept, worksp
                                                float(threshold) if threshold is not None else 0.0, int(apply_threshold), B, A,
                                                L.ptr(predicted_reward), L.ptr(loss), L.ptr(unweighted_loss), L.ptr(n_kept),
                                                L.ptr(dq), _ld(dq) if dq is not None else 0, L.ptr(workspace), L.stream_ptr()))
+
+
+# ---- multi-head self-attention and the transformer reward net's joins (attention.hip) ---------------------------------------
+def _rows_f32(t, rows, cols, what):
+    assert t.dtype == F32 and t.shape == (rows, cols) and t.stride(1) == 1, (what, t.dtype, t.shape, t.stride())
+    return t.stride(0)
+
+
+def _attn_check(T: int, B: int, E: int, nhead: int):
+    if nhead < 1 or E % nhead != 0:
+        raise NotImplementedError(f"attention: nhead {nhead} does not divide the embedding width {E}")
+    if not 1 <= T <= L.ATTN_MAX_SEQ_LEN:
+        raise NotImplementedError(f"attention: seq_len {T} is not supported (1 .. {L.ATTN_MAX_SEQ_LEN}: a lane per key)")
+    if E > L.ATTN_MAX_EMBED or E // nhead > L.ATTN_MAX_HEAD_DIM:
+        raise NotImplementedError(f"attention: width {E} with {nhead} heads is not supported (width up to {L.ATTN_MAX_EMBED}, "
+                                  f"head width up to {L.ATTN_MAX_HEAD_DIM})")
+    if T * B >= 1 << 29 or B * nhead >= 1 << 29:
+        raise NotImplementedError(f"attention: seq_len * batch = {T * B} is not supported (below 2^29)")
+
+
+def attn_forward(q, k, v, seq_len: int, batch: int, nhead: int, ctx, p=None):
+    """ctx [T * B, E] = softmax(q k^T / sqrt(E / nhead)) v per (b, head), rows ordered (t, b) (see rg_attn_forward); q, k, v
+    and ctx are fp32 [T * B, E] views with their own pitches; p (optional) [B, nhead, T, T] contiguous = the probabilities"""
+    _chk_dev(q, k, v, ctx, p)
+    T, B, E = int(seq_len), int(batch), q.shape[1]
+    _attn_check(T, B, E, nhead)
+    ld = [_rows_f32(t, T * B, E, n) for t, n in ((q, "q"), (k, "k"), (v, "v"), (ctx, "ctx"))]
+    if p is not None:
+        _f32_flat(p, B * nhead * T * T)
+    _run("rg_attn_forward", dict(T=T, B=B, E=E, nhead=nhead),
+         lambda: L.lib().rg_attn_forward(L.ptr(q), ld[0], L.ptr(k), ld[1], L.ptr(v), ld[2], T, B, E, int(nhead), L.ptr(ctx), ld[3],
+                                         L.ptr(p), L.stream_ptr()))
+
+
+def attn_backward(dctx, q, k, v, p, seq_len: int, batch: int, nhead: int, dq, dk, dv):
+    """dq, dk, dv [T * B, E] (written entirely; their own pitches) from d loss / d ctx, the forward's operands and its
+    probabilities p [B, nhead, T, T] (see rg_attn_backward)"""
+    _chk_dev(dctx, q, k, v, p, dq, dk, dv)
+    T, B, E = int(seq_len), int(batch), q.shape[1]
+    _attn_check(T, B, E, nhead)
+    ld = [_rows_f32(t, T * B, E, n) for t, n in ((dctx, "dctx"), (q, "q"), (k, "k"), (v, "v"), (dq, "dq"), (dk, "dk"), (dv, "dv"))]
+    _f32_flat(p, B * nhead * T * T)
+    _run("rg_attn_backward", dict(T=T, B=B, E=E, nhead=nhead),
+         lambda: L.lib().rg_attn_backward(L.ptr(dctx), ld[0], L.ptr(q), ld[1], L.ptr(k), ld[2], L.ptr(v), ld[3], L.ptr(p), T, B, E,
+                                          int(nhead), L.ptr(dq), ld[4], L.ptr(dk), ld[5], L.ptr(dv), ld[6], L.stream_ptr()))
+
+
+def residual_join(a, out, seq_len: int, batch: int, b=None, pe=None, relu: bool = False):
+    """out = act((a + b) + pe[row // batch]) on fp32 [T * B, E] views (see rg_residual_join): b and pe [>= T, E] optional, act
+    relu or linear, each element fp32 adds in that order"""
+    _chk_dev(a, out, b, pe)
+    T, B, E = int(seq_len), int(batch), a.shape[1]
+    if T * B >= 1 << 29:
+        raise NotImplementedError(f"residual_join: seq_len * batch = {T * B} is not supported (below 2^29)")
+    lda, ldo = _rows_f32(a, T * B, E, "a"), _rows_f32(out, T * B, E, "out")
+    ldb = _rows_f32(b, T * B, E, "b") if b is not None else 0
+    if pe is not None:
+        assert pe.dtype == F32 and pe.dim() == 2 and pe.shape[0] >= T and pe.shape[1] == E and pe.stride(1) == 1, pe.shape
+    _run("rg_residual_join", dict(N=T * B, E=E),
+         lambda: L.lib().rg_residual_join(L.ptr(a), lda, L.ptr(b), ldb, L.ptr(pe), pe.stride(0) if pe is not None else 0, T, B, E,
+                                          L.ACT["relu"] if relu else L.ACT["linear"], L.ptr(out), ldo, L.stream_ptr()))
+
+
+def residual_join_backward(grads, dx, out=None):
+    """dx = (((g0 + g1) + g2) + g3) over the one to four fp32 [N, E] gradient streams of grads, in their order, where the
+    join's saved relu output out is positive (out=None: a linear join) (see rg_residual_join_backward)"""
+    grads = list(grads)
+    assert 1 <= len(grads) <= 4, len(grads)
+    _chk_dev(dx, out, *grads)
+    N, E = dx.shape
+    if N >= 1 << 29:
+        raise NotImplementedError(f"residual_join_backward: {N} rows are not supported (below 2^29)")
+    ld_dx = _rows_f32(dx, N, E, "dx")
+    ldo = _rows_f32(out, N, E, "out") if out is not None else 0
+    gs = [(L.ptr(g), _rows_f32(g, N, E, "grad")) for g in grads] + [(None, 0)] * (4 - len(grads))
+    _run("rg_residual_join_backward", dict(N=N, E=E, streams=len(grads)),
+         lambda: L.lib().rg_residual_join_backward(L.ptr(out), ldo, gs[0][0], gs[0][1], gs[1][0], gs[1][1], gs[2][0], gs[2][1],
+                                                   gs[3][0], gs[3][1], N, E, L.ptr(dx), ld_dx, L.stream_ptr()))
