@@ -1608,6 +1608,68 @@ int rg_residual_join_backward(const float* out, int64_t ldo, const float* g0, in
                               const float* g2, int64_t ld2, const float* g3, int64_t ld3, int64_t rows, int cols, float* dx,
                               int64_t ld_dx, rg_stream_t stream);
 
+/* ---- Seq2Slate behind its encoder: embedding join, Frechet-sort likelihood and ranking (seq2slate.hip) --------------------
+ * Rows of the encoder's matrices are ordered (s, b): row s * batch + b of an fp32 [seq_len * batch, embed] view, as
+ * rg_attn_* reads them; candidate c of the reference's index space is c + 2 (0 = padding, 1 = the decoder's start symbol).
+ *
+ * rg_s2s_embed_join: src_embed[(s, b), :] = (sqrt(state_cols) * state_embed[b] | sqrt(cand_cols) * cand_embed[(s, b)]), the
+ * two Embedders' scalings with encode's repeat / reshape / cat (reagent/models/seq2slate.py:317-328, 776-796) in one launch;
+ * state_embed [batch, state_cols], cand_embed [seq_len * batch, cand_cols]; each element is one fp32 multiply by the root
+ * rounded to fp32.  rg_s2s_embed_join_backward: d_state_embed[b] = sqrt(state_cols) * sum_s d_src_embed[(s, b), :state_cols]
+ * (fp32 adds in ascending s, then one multiply), d_cand_embed = sqrt(cand_cols) * the right-hand slice.
+ *
+ * rg_frechet_head: PER_SEQ_LOG_PROB_MODE of a FRECHET_SORT net behind its encoder (decode, seq2slate.py:807-818;
+ * per_symbol_to_per_seq_probs, reagent/model_utils/seq2slate_utils.py:147-160) and Seq2SlateTrainer's loss
+ * (reagent/training/ranking/seq2slate_trainer.py:119-149, helper.py:10-18).  mem = the last encoder layer's output, w [embed]
+ * and bias [1] = encoder_scorer; tgt_out_idx [batch, tgt_len] int64 (pitch ld_idx), offset by 2, distinct in a row (a repeated
+ * index gives that row p = 1e-40 and no gradient; nothing is read or written through an index).
+ *   score[b, c] = w . mem[(c, b)] + bias;  pi_t = softmax of the scores over the candidates not chosen before step t;
+ *   p[b] = max(prod_t pi_t(a_t), 1e-40) (an fp32 subnormal: kept, not flushed);  log_prob = log p;  impt = p / logged;
+ *   clamped = impt (RG_IPS_CLAMP_NONE), clamp(impt, 0, clamp_max) (UNIVERSAL), where(impt > clamp_max, 0, impt) (AGGRESSIVE);
+ *   sums[0] = mean(-clamped * (reward - baseline)), sums[1] = mean(-impt * reward), sums[2] = mean(-clamped * reward)
+ * (baseline nullable: zeros).  With dscore .. dbias given (all four or none): d sums[0] / d score [batch, seq_len] =
+ * g_b * p_b * sum_{t : c remaining at t} (1[c = a_t] - pi_t(c)) with g_b = d sums[0] / d p_b by autograd's rule through each
+ * clamp (1e-40: where the product is at or above it; UNIVERSAL: where 0 <= impt <= clamp_max; AGGRESSIVE: where not
+ * impt > clamp_max), and from it dmem [seq_len * batch, embed] (written whole), dw [embed] and dbias [1].  logged null (then
+ * reward .. sums and the gradients must be null too): log_prob and p alone.  Everything is double on the fp32 inputs, each
+ * output rounded once; a wave owns a row, workgroups leave partials in workspace (rg_frechet_head_workspace doubles) which a
+ * second launch adds in workgroup order: no atomics, two runs give the same bits.
+ *
+ * rg_frechet_rank: RANK_MODE in one launch.  scores [batch, seq_len] given, or (scores null) computed from mem, w and bias as
+ * above.  RG_FRECHET_RANK_ENCODER (_encoder_rank): argsort of the scores, descending; RG_FRECHET_RANK_GREEDY (_greedy_rank):
+ * argsort of the first step's soft-max, descending; both with ties to the lower index, one-hot ranked_per_symbol_probs and
+ * ranked_per_seq_probs = 1.  RG_FRECHET_RANK_SAMPLED (_autoregressive_rank, greedy=False): tgt_len draws without
+ * replacement, each from its step's pi_t by inversion of the cumulative sum (double, ascending candidate order) at a
+ * Philox4x32-10 uniform, key = seed, counter = (row, step); the probabilities are the pi_t rows and ranked_per_seq_probs their
+ * product at the drawn indices, clamped at 1e-40.  The reference draws with torch.multinomial: the law is the same, the
+ * stream is not.  ranked_tgt_out_idx [batch, tgt_len] int64 (offset by 2), ranked_per_symbol_probs [batch, tgt_len,
+ * seq_len + 2] (columns 0 and 1 zero), ranked_per_seq_probs [batch], all contiguous and written whole.
+ *
+ * The soft-max's exponential holds its argument at -745: a remaining candidate more than 745 below the step's maximum weighs
+ * 4.9e-324 where the float64 statement has 0, which no sum, no rounded output and no draw sees.
+ *
+ * RG_EINVAL for tgt_len > seq_len, a pitch below its width, a missing pointer or an unknown method / mode; RG_EUNSUPPORTED
+ * for seq_len > RG_S2S_MAX_SEQ_LEN (a lane per candidate), embed (for the joins: state_cols + cand_cols) > RG_S2S_MAX_EMBED or
+ * seq_len * batch >= 2^29. */
+#define RG_S2S_MAX_SEQ_LEN 64
+#define RG_S2S_MAX_EMBED 512
+enum { RG_IPS_CLAMP_NONE = 0, RG_IPS_CLAMP_UNIVERSAL = 1, RG_IPS_CLAMP_AGGRESSIVE = 2 };
+enum { RG_FRECHET_RANK_ENCODER = 0, RG_FRECHET_RANK_GREEDY = 1, RG_FRECHET_RANK_SAMPLED = 2 };
+int rg_s2s_embed_join(const float* state_embed, int64_t ld_state, const float* cand_embed, int64_t ld_cand, int seq_len, int batch,
+                      int state_cols, int cand_cols, float* src_embed, int64_t ld_out, rg_stream_t stream);
+int rg_s2s_embed_join_backward(const float* d_src_embed, int64_t ld_d, int seq_len, int batch, int state_cols, int cand_cols,
+                               float* d_state_embed, int64_t ld_dstate, float* d_cand_embed, int64_t ld_dcand,
+                               rg_stream_t stream);
+size_t rg_frechet_head_workspace(int batch, int embed);
+int rg_frechet_head(const float* mem, int64_t ld_mem, const float* w, const float* bias, const int64_t* tgt_out_idx,
+                    int64_t ld_idx, const float* logged, const float* reward, const float* baseline, int clamp_method,
+                    double clamp_max, int seq_len, int tgt_len, int batch, int embed, float* log_prob, float* p, float* impt,
+                    float* clamped, float* sums, float* dscore, int64_t ld_dscore, float* dmem, int64_t ld_dmem, float* dw,
+                    float* dbias, double* workspace, rg_stream_t stream);
+int rg_frechet_rank(const float* scores, int64_t ld_scores, const float* mem, int64_t ld_mem, const float* w, const float* bias,
+                    int mode, uint64_t seed, int seq_len, int tgt_len, int batch, int embed, int64_t* ranked_tgt_out_idx,
+                    float* ranked_per_symbol_probs, float* ranked_per_seq_probs, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,9 @@ LINUCB_MAX_DIM = 512  # RG_LINUCB_MAX_DIM: the LinUCB kernels' limit on the feat
 LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (the matrix lives in one workgroup's registers)
 LSTM_MAX_HIDDEN, LSTM_MAX_LAYERS = 256, 4  # RG_LSTM_MAX_HIDDEN, RG_LSTM_MAX_LAYERS: the LSTM kernels' limits
 ATTN_MAX_SEQ_LEN, ATTN_MAX_HEAD_DIM, ATTN_MAX_EMBED = 64, 128, 512  # RG_ATTN_MAX_*: the attention kernels' limits
+S2S_MAX_SEQ_LEN, S2S_MAX_EMBED = 64, 512  # RG_S2S_MAX_*: the Seq2Slate kernels' limits (a lane per candidate)
+IPS_CLAMP_NONE, IPS_CLAMP_UNIVERSAL, IPS_CLAMP_AGGRESSIVE = 0, 1, 2  # RG_IPS_CLAMP_*: rg_frechet_head's clamp methods
+FRECHET_RANK_ENCODER, FRECHET_RANK_GREEDY, FRECHET_RANK_SAMPLED = 0, 1, 2  # RG_FRECHET_RANK_*: rg_frechet_rank's modes
 MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
 STEP_CE_MAX_CLASSES = 32  # RG_STEP_CE_MAX_CLASSES: rg_step_ce_head's limit (Seq2Reward's multi_steps)
 CEM_MAX_MODELS, CEM_MAX_HORIZON, CEM_MAX_INPUT = 16, 64, 512  # RG_CEM_MAX_*: the CEM planner kernels' limits
@@ -396,6 +399,13 @@ SIGNATURES = {
     "rg_attn_backward": (c_int, [c_void_p, c_i64] * 4 + [c_void_p] + [c_int] * 4 + [c_void_p, c_i64] * 3 + [c_void_p]),
     "rg_residual_join": (c_int, [c_void_p, c_i64] * 3 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
     "rg_residual_join_backward": (c_int, [c_void_p, c_i64] * 5 + [c_i64, c_int, c_void_p, c_i64, c_void_p]),
+    "rg_s2s_embed_join": (c_int, [c_void_p, c_i64] * 2 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
+    "rg_s2s_embed_join_backward": (c_int, [c_void_p, c_i64] + [c_int] * 4 + [c_void_p, c_i64] * 2 + [c_void_p]),
+    "rg_frechet_head_workspace": (c_sz, [c_int, c_int]),
+    "rg_frechet_head": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64] + [c_void_p] * 3 + [c_int, c_d]
+                        + [c_int] * 4 + [c_void_p] * 5 + [c_void_p, c_i64] * 2 + [c_void_p] * 3 + [c_void_p]),
+    "rg_frechet_rank": (c_int, [c_void_p, c_i64] * 2 + [c_void_p, c_void_p, c_int, ctypes.c_uint64] + [c_int] * 4
+                        + [c_void_p] * 3 + [c_void_p]),
 }
 
 _lib = None

@@ -2,7 +2,7 @@
 
 Only what the DQN / QR-DQN / SAC hot path touches: FeatureData (:312-347), ExtraData (:440-450),
 ActorOutput (:245-249), DocList (:252-288), BaseInput (:688-769), DiscreteDqnInput (:772-816), SlateQInput (:819-863),
-ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), SyntheticRewardNetworkOutput, BanditRewardModelInput (:977-995), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
+ParametricDqnInput (:866-896), PolicyNetworkInput (:899-915), PolicyGradientInput (:918-974), MemoryNetworkInput (:1017-1046), MemoryNetworkOutput (:1057-1066), Seq2RewardOutput (:1069-1071), SyntheticRewardNetworkOutput, BanditRewardModelInput (:977-995), PreprocessedRankingInput (:453-685), RankingOutput (:1091-1113), CBInput (:1136-1207) and the tensor-method forwarding of TensorDataClass (:49-108).  The trainers in this
 package only read attributes, so instances of the reference's own classes work as well.
 
 When the reference package itself is importable (a ReAgent installation this package is dropped into), its OWN
@@ -483,6 +483,125 @@ class BanditRewardModelInput(TensorDataClass):
         return self.state.float_features.size()[0]
 
 
+def _rows_at(data: torch.Tensor, index_2d: torch.Tensor) -> torch.Tensor:
+    """out[b, j] = data[b, index_2d[b, j]] for data [B, N, D] and index_2d [B, M] (the reference's torch_utils.gather)"""
+    return data.gather(1, index_2d.unsqueeze(2).expand(-1, -1, data.shape[2]))
+
+
+@dataclass
+class PreprocessedRankingInput(TensorDataClass):
+    """:453-685 — a ranking batch: the state [B, state_dim], the candidates src_seq [B, S, candidate_dim], the logged slate as
+    indices (offset by 2: 0 is the padding symbol and 1 the decoder's start symbol) and as gathered feature rows, its logged
+    propensity tgt_out_probs [B, 1] and the slate's reward [B, 1].  The feature members are FeatureData: bare tensors go
+    through from_tensors (or from_input, which derives the index and mask members)."""
+
+    state: FeatureData
+    src_seq: FeatureData
+    src_src_mask: Optional[torch.Tensor] = None
+    tgt_in_seq: Optional[FeatureData] = None
+    tgt_out_seq: Optional[FeatureData] = None
+    tgt_tgt_mask: Optional[torch.Tensor] = None
+    slate_reward: Optional[torch.Tensor] = None
+    position_reward: Optional[torch.Tensor] = None
+    src_in_idx: Optional[torch.Tensor] = None
+    tgt_in_idx: Optional[torch.Tensor] = None
+    tgt_out_idx: Optional[torch.Tensor] = None
+    tgt_out_probs: Optional[torch.Tensor] = None
+    # the ground-truth slate, where there is one
+    optim_tgt_in_idx: Optional[torch.Tensor] = None
+    optim_tgt_out_idx: Optional[torch.Tensor] = None
+    optim_tgt_in_seq: Optional[FeatureData] = None
+    optim_tgt_out_seq: Optional[FeatureData] = None
+    extras: Optional[ExtraData] = field(default_factory=ExtraData)
+
+    _FEATURE_MEMBERS = ("state", "src_seq", "tgt_in_seq", "tgt_out_seq", "optim_tgt_in_seq", "optim_tgt_out_seq")
+
+    def __post_init__(self):
+        if any(isinstance(getattr(self, n), torch.Tensor) for n in self._FEATURE_MEMBERS):
+            raise ValueError("Use from_tensors() " + " ".join(str(type(getattr(self, n))) for n in self._FEATURE_MEMBERS) + " ")
+
+    def batch_size(self) -> int:
+        return self.state.float_features.size()[0]
+
+    def __len__(self) -> int:
+        return self.batch_size()
+
+    @classmethod
+    def from_input(cls, state, candidates, device, action=None, optimal_action=None, logged_propensities=None, slate_reward=None,
+                   position_reward=None, extras=None):
+        """the derived members from raw input: action / optimal_action [B, T] index the candidates from 0"""
+        assert len(state.shape) == 2 and len(candidates.shape) == 3
+        state, candidates = state.to(device), candidates.to(device)
+        B, S, D = candidates.shape
+        if action is not None:
+            assert len(action.shape) == 2
+            action = action.to(device)
+        if logged_propensities is not None:
+            assert len(logged_propensities.shape) == 2 and logged_propensities.shape[1] == 1
+            logged_propensities = logged_propensities.to(device)
+        if slate_reward is not None:
+            assert len(slate_reward.shape) == 2 and slate_reward.shape[1] == 1
+            slate_reward = slate_reward.to(device)
+        if position_reward is not None:
+            assert position_reward.shape == action.shape
+            position_reward = position_reward.to(device)
+
+        def target_members(a):
+            """(tgt_in_idx, tgt_out_idx, tgt_in_seq, tgt_out_seq, tgt_tgt_mask) of a slate: the decoder's input is its output
+            shifted by one step behind the start symbol, whose features are zeros"""
+            if a is None:
+                return None, None, None, None, None
+            T = a.shape[1]
+            out_idx = a + 2
+            in_idx = torch.full((B, T), 1, device=device)  # DECODER_START_SYMBOL
+            in_idx[:, 1:] = out_idx[:, :-1]
+            out_seq = _rows_at(torch.cat((torch.zeros(B, 2, D, device=device), candidates), dim=1), out_idx)
+            in_seq = torch.zeros(B, T, D, device=device)
+            in_seq[:, 1:] = out_seq[:, :-1]
+            mask = ~torch.triu(torch.ones(1, T, T, device=device, dtype=torch.bool), diagonal=1)  # subsequent_mask
+            return in_idx, out_idx, in_seq, out_seq, mask
+
+        tgt_in_idx, tgt_out_idx, tgt_in_seq, tgt_out_seq, tgt_tgt_mask = target_members(action)
+        optim_in_idx, optim_out_idx, optim_in_seq, optim_out_seq, _ = target_members(optimal_action)
+        return cls.from_tensors(
+            state=state, src_seq=candidates, src_src_mask=torch.ones(B, S, S, device=device).type(torch.int8),
+            tgt_in_seq=tgt_in_seq, tgt_out_seq=tgt_out_seq, tgt_tgt_mask=tgt_tgt_mask, slate_reward=slate_reward,
+            position_reward=position_reward, src_in_idx=torch.arange(S, device=device).repeat(B, 1) + 2, tgt_in_idx=tgt_in_idx,
+            tgt_out_idx=tgt_out_idx, tgt_out_probs=logged_propensities, optim_tgt_in_idx=optim_in_idx,
+            optim_tgt_out_idx=optim_out_idx, optim_tgt_in_seq=optim_in_seq, optim_tgt_out_seq=optim_out_seq, extras=extras)
+
+    @classmethod
+    def from_tensors(cls, state, src_seq, src_src_mask=None, tgt_in_seq=None, tgt_out_seq=None, tgt_tgt_mask=None,
+                     slate_reward=None, position_reward=None, src_in_idx=None, tgt_in_idx=None, tgt_out_idx=None, tgt_out_probs=None,
+                     optim_tgt_in_idx=None, optim_tgt_out_idx=None, optim_tgt_in_seq=None, optim_tgt_out_seq=None, extras=None,
+                     **kwargs):
+        given = dict(src_src_mask=src_src_mask, tgt_in_seq=tgt_in_seq, tgt_out_seq=tgt_out_seq, tgt_tgt_mask=tgt_tgt_mask,
+                     slate_reward=slate_reward, position_reward=position_reward, src_in_idx=src_in_idx, tgt_in_idx=tgt_in_idx,
+                     tgt_out_idx=tgt_out_idx, tgt_out_probs=tgt_out_probs, optim_tgt_in_idx=optim_tgt_in_idx,
+                     optim_tgt_out_idx=optim_tgt_out_idx, optim_tgt_in_seq=optim_tgt_in_seq, optim_tgt_out_seq=optim_tgt_out_seq)
+        assert isinstance(state, torch.Tensor) and isinstance(src_seq, torch.Tensor)
+        for name, t in given.items():
+            assert t is None or isinstance(t, torch.Tensor), name
+        assert extras is None or isinstance(extras, ExtraData)
+        wrap = lambda t: FeatureData(float_features=t) if t is not None else None  # noqa: E731
+        for name in ("tgt_in_seq", "tgt_out_seq", "optim_tgt_in_seq", "optim_tgt_out_seq"):
+            given[name] = wrap(given[name])
+        return cls(state=FeatureData(float_features=state), src_seq=FeatureData(float_features=src_seq), extras=extras, **given)
+
+
+@dataclass
+class RankingOutput(TensorDataClass):
+    """:1091-1124 — what a ranking net returns: the ranked slate's indices [B, T] (offset by 2), its per-step probabilities
+    [B, T, S + 2] and per-sequence probability [B, 1] (rank mode); the logged slate's log-probability [B, 1]; the encoder's
+    scores [B, T]"""
+
+    ranked_tgt_out_idx: Optional[torch.Tensor] = None
+    ranked_per_symbol_probs: Optional[torch.Tensor] = None
+    ranked_per_seq_probs: Optional[torch.Tensor] = None
+    log_probs: Optional[torch.Tensor] = None
+    encoder_scores: Optional[torch.Tensor] = None
+
+
 # ---- the reference's own classes, when it is importable (see the module docstring) ---------------------------
 def _reference_types():
     import importlib.util
@@ -505,7 +624,8 @@ _ref = _reference_types()
 if _ref is not None:
     for _name in ("TensorDataClass", "ActorOutput", "DocList", "FeatureData", "ExtraData", "BaseInput", "DiscreteDqnInput",
                   "SlateQInput", "ParametricDqnInput", "PolicyNetworkInput", "PolicyGradientInput", "CBInput", "MemoryNetworkInput",
-                  "MemoryNetworkOutput", "Seq2RewardOutput", "SyntheticRewardNetworkOutput", "BanditRewardModelInput"):
+                  "MemoryNetworkOutput", "Seq2RewardOutput", "SyntheticRewardNetworkOutput", "BanditRewardModelInput",
+                  "PreprocessedRankingInput", "RankingOutput"):
         globals()[_name] = getattr(_ref, _name)
     USING_REFERENCE_TYPES = True
 del _ref

@@ -20,3 +20,4 @@ from .synthetic_reward import (  # noqa: F401
     SyntheticRewardNet,
 )
 from .synthetic_reward_transformer import TransformerSyntheticRewardNet  # noqa: F401
+from .seq2slate import BaselineNet, Seq2SlateTransformerNet, Seq2SlateTransformerOutput  # noqa: F401

@@ -47,7 +47,8 @@ import torch.nn as nn
 from .. import _lib as L
 from .. import ops
 from ..engine import FCStack
-from . import lstm_stack
+from . import encoder_ops
+from .encoder_ops import block as _block
 from .fully_connected_network import _Activation
 from .synthetic_reward import _act_code, _RewardTrunk
 
@@ -99,13 +100,6 @@ class _Encoder(nn.Module):
         self.layers = nn.ModuleList([copy.deepcopy(layer) for _ in range(num_layers)])
 
 
-def _block(first, second):
-    """a two-linear block Linear -> relu -> Linear as an fp32 FC stack that also returns d loss / d its input"""
-    st = FCStack([first.weight, second.weight], [first.bias, second.bias], [L.ACT["relu"], L.ACT["linear"]], L.PREC_F32)
-    st.set_need_input_grad(True)
-    return st
-
-
 class TransformerSyntheticRewardNet(_RewardTrunk):
     def __init__(
         self,
@@ -153,7 +147,7 @@ class TransformerSyntheticRewardNet(_RewardTrunk):
         self.transformer = _Encoder(_EncoderLayer(d_model, nhead, dim_feedforward, layer_norm_eps, max_len), num_encoder_layers)
         self.fc_out = nn.Linear(d_model, 1)
         self.output_activation = _Activation(last_layer_activation)
-        self._wt = {}  # name -> (version key, W^T of a dgrad), remade when the parameter has changed
+        self._transposed = encoder_ops.TransposedCache()  # W^T of the dgrads, remade when a parameter has changed
         self._stacks = None
 
     # ---- what _RewardTrunk asks of a subclass ------------------------------------------------------------------------------
@@ -173,22 +167,7 @@ class TransformerSyntheticRewardNet(_RewardTrunk):
             self._stacks = (FCStack([lin.weight], [lin.bias], [L.ACT["relu"]], L.PREC_F32), layers)
         return self._stacks
 
-    def _transposed(self, name, p, rows):
-        """the transposed copy [in, out] of rows `rows` of parameter p, for rg_fc_dgrad"""
-        key = (p._version, getattr(p, "_rg_version", 0), p.data_ptr())
-        rec = self._wt.get(name)
-        if rec is None or rec[0] != key or rec[1].device != p.device:
-            rec = self._wt[name] = (key, lstm_stack.transposed(p.detach()[rows]))
-        return rec[1]
-
-    @staticmethod
-    def _stack_forward(st, x, save):
-        """-> (the stack's output [N, out] and, with save, the transposed staged input the weight gradient reads)"""
-        st.stage_weights(need_transposed=True)
-        xc, xt = st.stage_input(x, need_transposed=save)
-        out = torch.empty(x.shape[0], st.dims[-1], dtype=F32, device=x.device)
-        st.forward(xc, out, save=save)
-        return out, xt
+    _stack_forward = staticmethod(encoder_ops.stack_forward)
 
     def _layer_forward(self, m, st, x, T, B, save):
         N, E = x.shape
@@ -254,11 +233,7 @@ class TransformerSyntheticRewardNet(_RewardTrunk):
         G = lambda p: grad[id(p)]  # noqa: E731
 
         def layer_norm_backward(ln, g, pre, stats):
-            dz = new(N, E)
-            nb = L.lib().rg_layer_norm_backward_workspace_bytes(N, E)
-            ops.layer_norm_backward(g, pre, stats[0], stats[1], ln.weight.detach(), G(ln.weight), G(ln.bias),
-                                    torch.empty((nb + 15) // 16 * 4, dtype=F32, device=dev), dz32=dz)
-            return dz
+            return encoder_ops.layer_norm_backward(ln, g, pre, stats, G(ln.weight), G(ln.bias))
 
         def block_backward(stack, dout, xt, first, second):
             dx = new(N, E)
@@ -267,10 +242,7 @@ class TransformerSyntheticRewardNet(_RewardTrunk):
 
         def linear_backward(dz, x_in, name, w, b, rows=slice(None)):
             """d input of x_in W^T + b for rows `rows` of the parameters w and b and, into their gradients, dW and db"""
-            dx = new(N, w.shape[1])
-            ops.fc_dgrad(dz, self._transposed(f"{name}{i}", w, rows), None, L.ACT["linear"], L.PREC_F32, dx32=dx)
-            lstm_stack.wgrad(lstm_stack.transposed(dz), lstm_stack.transposed(x_in), G(w)[rows], G(b)[rows], N)
-            return dx
+            return encoder_ops.linear_backward(self._transposed, dz, x_in, f"{name}{i}", w, G(w), G(b), rows)
 
         # y = LayerNorm2(s1 + ff(s1)), s1 = LayerNorm1(z + out_proj(ctx))
         dpre2 = layer_norm_backward(m.norm2, dy, t["pre2"], t["ln2"])

@@ -2009,3 +2009,114 @@ def residual_join_backward(grads, dx, out=None):
     _run("rg_residual_join_backward", dict(N=N, E=E, streams=len(grads)),
          lambda: L.lib().rg_residual_join_backward(L.ptr(out), ldo, gs[0][0], gs[0][1], gs[1][0], gs[1][1], gs[2][0], gs[2][1],
                                                    gs[3][0], gs[3][1], N, E, L.ptr(dx), ld_dx, L.stream_ptr()))
+
+
+# ---- Seq2Slate behind its encoder: embedding join, Frechet-sort likelihood and ranking (seq2slate.hip) ----------------------
+def _s2s_check(S: int, T: int, B: int, E: int):
+    if not 1 <= S <= L.S2S_MAX_SEQ_LEN:
+        raise NotImplementedError(f"seq2slate: src_seq_len {S} is not supported (1 .. {L.S2S_MAX_SEQ_LEN}: a lane per candidate)")
+    if not 1 <= T <= S:
+        raise NotImplementedError(f"seq2slate: tgt_seq_len {T} is not supported (1 .. src_seq_len = {S})")
+    if not 1 <= E <= L.S2S_MAX_EMBED:
+        raise NotImplementedError(f"seq2slate: dim_model {E} is not supported (1 .. {L.S2S_MAX_EMBED})")
+    if B < 1 or S * B >= 1 << 29:
+        raise NotImplementedError(f"seq2slate: src_seq_len * batch = {S * B} is not supported (1 .. below 2^29)")
+
+
+def s2s_embed_join(state_embed, cand_embed, seq_len: int, batch: int, src_embed):
+    """src_embed [S * B, Es + Ec] = (sqrt(Es) * state_embed[b] | sqrt(Ec) * cand_embed[(s, b)]), rows ordered (s, b) (see
+    rg_s2s_embed_join); state_embed [B, Es], cand_embed [S * B, Ec], fp32 views with their own pitches"""
+    _chk_dev(state_embed, cand_embed, src_embed)
+    S, B, Es, Ec = int(seq_len), int(batch), state_embed.shape[1], cand_embed.shape[1]
+    _s2s_check(S, 1, B, Es + Ec)
+    ld = [_rows_f32(state_embed, B, Es, "state_embed"), _rows_f32(cand_embed, S * B, Ec, "cand_embed"),
+          _rows_f32(src_embed, S * B, Es + Ec, "src_embed")]
+    _run("rg_s2s_embed_join", dict(N=S * B, Es=Es, Ec=Ec),
+         lambda: L.lib().rg_s2s_embed_join(L.ptr(state_embed), ld[0], L.ptr(cand_embed), ld[1], S, B, Es, Ec, L.ptr(src_embed),
+                                           ld[2], L.stream_ptr()))
+
+
+def s2s_embed_join_backward(d_src_embed, seq_len: int, batch: int, d_state_embed, d_cand_embed):
+    """d_state_embed [B, Es] = sqrt(Es) * the sum over s (ascending) of d_src_embed's left Es columns, d_cand_embed [S * B, Ec]
+    = sqrt(Ec) * its right Ec columns (see rg_s2s_embed_join_backward)"""
+    _chk_dev(d_src_embed, d_state_embed, d_cand_embed)
+    S, B, Es, Ec = int(seq_len), int(batch), d_state_embed.shape[1], d_cand_embed.shape[1]
+    _s2s_check(S, 1, B, Es + Ec)
+    ld = [_rows_f32(d_src_embed, S * B, Es + Ec, "d_src_embed"), _rows_f32(d_state_embed, B, Es, "d_state_embed"),
+          _rows_f32(d_cand_embed, S * B, Ec, "d_cand_embed")]
+    _run("rg_s2s_embed_join_backward", dict(N=S * B, Es=Es, Ec=Ec),
+         lambda: L.lib().rg_s2s_embed_join_backward(L.ptr(d_src_embed), ld[0], S, B, Es, Ec, L.ptr(d_state_embed), ld[1],
+                                                    L.ptr(d_cand_embed), ld[2], L.stream_ptr()))
+
+
+def frechet_head_workspace(batch: int, embed: int) -> int:
+    """doubles of workspace rg_frechet_head asks for"""
+    return int(L.lib().rg_frechet_head_workspace(batch, embed))
+
+
+def _s2s_scorer(w, bias, E):
+    assert w.dtype == F32 and w.is_contiguous() and w.numel() == E, ("encoder_scorer.weight", w.dtype, w.shape)
+    assert bias.dtype == F32 and bias.numel() == 1, ("encoder_scorer.bias", bias.dtype, bias.shape)
+
+
+def frechet_head(mem, w, bias, tgt_out_idx, seq_len: int, batch: int, log_prob, p, workspace, logged=None, reward=None,
+                 baseline=None, clamp_method: int = 0, clamp_max: float = 0.0, impt=None, clamped=None, sums=None, dscore=None,
+                 dmem=None, dw=None, dbias=None):
+    """the Frechet-sort sequence likelihood behind the encoder and Seq2SlateTrainer's loss (see rg_frechet_head): mem [S * B, E]
+    rows (s, b), w [E] and bias [1] the encoder scorer, tgt_out_idx [B, T] int64 offset by 2; log_prob, p [B].  With logged and
+    reward [B] (baseline [B] optional): impt, clamped [B] and sums [3] = the loss and the unclamped and clamped IPS means;
+    with dscore [B, S], dmem [S * B, E], dw [E] and dbias [1] the loss's gradients"""
+    _chk_dev(mem, w, bias, tgt_out_idx, log_prob, p, workspace, logged, reward, baseline, impt, clamped, sums, dscore, dmem, dw,
+             dbias)
+    S, B, E = int(seq_len), int(batch), mem.shape[1]
+    assert tgt_out_idx.dtype == torch.int64 and tgt_out_idx.dim() == 2 and tgt_out_idx.shape[0] == B, tgt_out_idx.shape
+    assert tgt_out_idx.stride(1) == 1
+    T = tgt_out_idx.shape[1]
+    _s2s_check(S, T, B, E)
+    ld_mem = _rows_f32(mem, S * B, E, "mem")
+    _s2s_scorer(w, bias, E)
+    for t in (log_prob, p, logged, reward, baseline, impt, clamped):
+        _f32_flat(t, B)
+    _f32_flat(sums, 3)
+    assert workspace.dtype == torch.float64 and workspace.is_contiguous() and workspace.numel() >= frechet_head_workspace(B, E)
+    train = dscore is not None
+    assert all((t is not None) == train for t in (dmem, dw, dbias)), "dscore, dmem, dw and dbias come together"
+    assert (logged is None) == (reward is None) == (impt is None) == (clamped is None) == (sums is None)
+    assert logged is not None or (baseline is None and not train), "the loss needs logged propensities and rewards"
+    ld_ds = _rows_f32(dscore, B, S, "dscore") if train else 0
+    ld_dm = _rows_f32(dmem, S * B, E, "dmem") if train else 0
+    if train:
+        _f32_flat(dw, E)
+        _f32_flat(dbias, 1)
+    _run("rg_frechet_head", dict(S=S, T=T, B=B, E=E, train=train),
+         lambda: L.lib().rg_frechet_head(L.ptr(mem), ld_mem, L.ptr(w), L.ptr(bias), L.ptr(tgt_out_idx), tgt_out_idx.stride(0),
+                                         L.ptr(logged), L.ptr(reward), L.ptr(baseline), int(clamp_method), float(clamp_max), S, T,
+                                         B, E, L.ptr(log_prob), L.ptr(p), L.ptr(impt), L.ptr(clamped), L.ptr(sums), L.ptr(dscore),
+                                         ld_ds, L.ptr(dmem), ld_dm, L.ptr(dw), L.ptr(dbias), L.ptr(workspace), L.stream_ptr()))
+
+
+def frechet_rank(mode: int, seq_len: int, batch: int, ranked_tgt_out_idx, ranked_per_symbol_probs, ranked_per_seq_probs,
+                 scores=None, mem=None, w=None, bias=None, seed: int = 0):
+    """RANK_MODE in one launch (see rg_frechet_rank): from scores [B, S], or from mem [S * B, E], w [E] and bias [1]; mode
+    L.FRECHET_RANK_ENCODER / _GREEDY (argsort, one-hot probabilities) or _SAMPLED (draws without replacement keyed by seed).
+    ranked_tgt_out_idx [B, T] int64 (offset by 2), ranked_per_symbol_probs [B, T, S + 2], ranked_per_seq_probs [B]"""
+    _chk_dev(ranked_tgt_out_idx, ranked_per_symbol_probs, ranked_per_seq_probs, scores, mem, w, bias)
+    S, B = int(seq_len), int(batch)
+    assert ranked_tgt_out_idx.dtype == torch.int64 and ranked_tgt_out_idx.dim() == 2 and ranked_tgt_out_idx.is_contiguous()
+    assert ranked_tgt_out_idx.shape[0] == B, ranked_tgt_out_idx.shape
+    T = ranked_tgt_out_idx.shape[1]
+    assert (scores is None) != (mem is None), "scores, or mem with the scorer"
+    E = mem.shape[1] if mem is not None else 1
+    _s2s_check(S, T, B, E)
+    if mode not in (L.FRECHET_RANK_ENCODER, L.FRECHET_RANK_GREEDY, L.FRECHET_RANK_SAMPLED):
+        raise NotImplementedError(f"frechet_rank: mode {mode} is not one of the three ranking modes")
+    ld_s = _rows_f32(scores, B, S, "scores") if scores is not None else 0
+    ld_m = _rows_f32(mem, S * B, E, "mem") if mem is not None else 0
+    if mem is not None:
+        _s2s_scorer(w, bias, E)
+    _f32_flat(ranked_per_symbol_probs, B * T * (S + 2))
+    _f32_flat(ranked_per_seq_probs, B)
+    _run("rg_frechet_rank", dict(S=S, T=T, B=B, E=E, mode=int(mode)),
+         lambda: L.lib().rg_frechet_rank(L.ptr(scores), ld_s, L.ptr(mem), ld_m, L.ptr(w), L.ptr(bias), int(mode),
+                                         int(seed) & 0xFFFFFFFFFFFFFFFF, S, T, B, E, L.ptr(ranked_tgt_out_idx),
+                                         L.ptr(ranked_per_symbol_probs), L.ptr(ranked_per_seq_probs), L.stream_ptr()))

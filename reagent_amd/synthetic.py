@@ -433,3 +433,26 @@ class ScriptedAgent:
         sp = self.env.action_space
         frac = ((k * 3 + np.arange(sp.low.size) * 5) % 8) / 8.0  # inside [low, high): rescale_actions asserts the range
         return (sp.low + frac.astype(np.float32) * (sp.high - sp.low)).astype(np.float32), log_prob
+
+
+def ranking_batch(batch: int, src_seq_len: int, tgt_seq_len: int, state_dim: int, candidate_dim: int, seed: int = 0, device=None):
+    """A seeded rlt.PreprocessedRankingInput of logged slates, built through from_input: state randn [B, state_dim], candidates
+    randn [B, S, candidate_dim], the logged slate action [B, T] = the first T of a random permutation of the S candidates (distinct
+    in a row), its logged propensity in [0.05, 1) (strictly positive) and slate_reward [B, 1] = a fixed linear function (weights
+    from the shapes: every batch has the same task) of the state and of the chosen candidates, earlier positions weighing more,
+    plus 0.1 randn"""
+    from .core import types as rlt
+
+    B, S, T = batch, src_seq_len, tgt_seq_len
+    assert 1 <= T <= S, (T, S)
+    task = torch.Generator().manual_seed(1000 * state_dim + candidate_dim)
+    w_state, w_cand = torch.randn(state_dim, generator=task), torch.randn(candidate_dim, generator=task)
+    g = torch.Generator().manual_seed(seed)
+    state, candidates = torch.randn(B, state_dim, generator=g), torch.randn(B, S, candidate_dim, generator=g)
+    action = torch.stack([torch.randperm(S, generator=g)[:T] for _ in range(B)])
+    logged = 0.05 + 0.95 * torch.rand(B, 1, generator=g)
+    chosen = candidates.gather(1, action.unsqueeze(2).expand(B, T, candidate_dim))
+    position = 1.0 / torch.arange(1, T + 1, dtype=torch.float32)
+    reward = (state @ w_state).view(B, 1) + ((chosen @ w_cand) * position).sum(dim=1, keepdim=True) + 0.1 * torch.randn(B, 1, generator=g)
+    return rlt.PreprocessedRankingInput.from_input(state=state, candidates=candidates, device=device if device is not None else "cpu",
+                                                   action=action, logged_propensities=logged, slate_reward=reward)

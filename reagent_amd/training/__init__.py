@@ -13,6 +13,7 @@ from .cem_trainer import CEMTrainer  # noqa: F401
 from .reward_network_trainer import LossFunction, RewardNetTrainer  # noqa: F401
 from .cfeval import BanditRewardNetTrainer  # noqa: F401
 from .cb import DeepRepresentLinUCBTrainer, DisjointLinUCBTrainer, LinUCBTrainer  # noqa: F401
+from .ranking import Seq2SlateTrainer  # noqa: F401
 from .parameters import (  # noqa: F401
     C51TrainerParameters,
     CRRTrainerParameters,
@@ -23,6 +24,7 @@ from .parameters import (  # noqa: F401
     ReinforceTrainerParameters,
     RewardNetworkTrainerParameters,
     SACTrainerParameters,
+    Seq2SlateTrainerParameters,
     SlateQTrainerParameters,
     TD3TrainerParameters,
 )

@@ -14,6 +14,7 @@ import inspect
 from typing import get_args
 
 from ..core.parameters import EvaluationParameters, RLParameters
+from ..core.parameters_seq2slate import Seq2SlateParameters
 from ..optimizer import Optimizer__Union
 from .c51_trainer import C51Trainer
 from .discrete_crr_trainer import DiscreteCRRTrainer
@@ -22,6 +23,7 @@ from .parametric_dqn_trainer import ParametricDQNTrainer
 from .ppo_trainer import PPOTrainer
 from .qrdqn_trainer import QRDQNTrainer
 from .reinforce_trainer import ReinforceTrainer
+from .ranking.seq2slate_trainer import Seq2SlateTrainer
 from .reward_network_trainer import RewardNetTrainer
 from .sac_trainer import SACTrainer
 from .slate_q_trainer import SlateQTrainer
@@ -129,6 +131,12 @@ class ReinforceTrainerParameters:
 @make_config_class(PPOTrainer.__init__, blocklist=["policy", "value_net"])
 class PPOTrainerParameters:
     """parameters.py:142-150"""
+
+
+@make_config_class(Seq2SlateTrainer.__init__, blocklist=["use_gpu", "seq2slate_net", "baseline_net", "baseline_warmup_num_batches"],
+                   factories={"params": Seq2SlateParameters})
+class Seq2SlateTrainerParameters:
+    """parameters.py:139-151"""
 
 
 @make_config_class(RewardNetTrainer.__init__, blocklist=["reward_net"])

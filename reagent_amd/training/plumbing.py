@@ -292,3 +292,18 @@ def note_graph_replays(tr, n: int):
             for p in g["params"]:
                 p._rg_version = getattr(p, "_rg_version", 0) + 1
     tr.all_batches_processed += n
+
+
+def accumulating_backward(slab, params, trained, backward):
+    """A HIP backward that OVERWRITES the gradient slab, made to accumulate over several batches (a trainer that steps its
+    optimizer every k-th batch): the gradients still published through p.grad since the last zero_grad(set_to_none=True) are
+    kept, `backward()` runs, and they are added back.  Only the parameters of `trained` (a subset of the slab's `params`) are
+    published; the others keep p.grad = None, so an optimizer over all of `params` skips them as torch's would."""
+    trained_ids = {id(p) for p in trained}
+    held = [(i, slab.view(slab.grad, i).clone()) for i, p in enumerate(params) if id(p) in trained_ids and p.grad is not None]
+    backward()
+    for i, g in held:
+        slab.view(slab.grad, i).add_(g)
+    for i, p in enumerate(params):
+        if id(p) in trained_ids:
+            p.grad = slab.view(slab.grad, i)
