@@ -20,8 +20,11 @@ __host__ __device__ inline int bn_chunks(int batch) {
 }
 
 // partial column sums over a row chunk: parts[chunk][0][c] = sum a, parts[chunk][1][c] = sum b where
-//   STATS: a = x, b = x * x;     GRADS: a = g, b = g * xhat, xhat = (x - mean[c]) * rstd[c]
-// (rstd null: 1 / sqrt(var[c] + eps), the frozen statistics of eval mode)
+//   STATS: a = d, b = d * d, d = x - x[0, c];     GRADS: a = g, b = g * xhat, xhat = (x - mean[c]) * rstd[c]
+// (rstd null: 1 / sqrt(var[c] + eps), the frozen statistics of eval mode).  STATS sums are SHIFTED by the column's first
+// row, the same shift in every chunk (the difference of two floats is exact in double): E[d^2] - E[d]^2 cancels against
+// the distance of x[0, c] from the mean, a few standard deviations, where E[x^2] - E[x]^2 cancelled against the mean
+// itself and lost a column of mean 4096 and deviation 0.01 five digits of its rstd.
 template <bool GRADS>
 __global__ void bn_partial_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ g, long ldg,
                                   const float* __restrict__ mean, const float* __restrict__ rstd,
@@ -34,6 +37,7 @@ __global__ void bn_partial_kernel(const float* __restrict__ x, long ldx, const f
   double sa = 0.0, sb = 0.0;
   if (c < n) {
     const float m = GRADS ? mean[c] : 0.f, rs = GRADS ? (rstd ? rstd[c] : 1.f / sqrtf(var[c] + eps)) : 0.f;
+    const double shift = GRADS ? 0.0 : (double)x[c];
     for (int r = r0 + w; r < r1; r += BN_WAVES) {
       const float xv = x[(long)r * ldx + c];
       if (GRADS) {
@@ -41,8 +45,9 @@ __global__ void bn_partial_kernel(const float* __restrict__ x, long ldx, const f
         sa += (double)gv;
         sb += (double)gv * (double)((xv - m) * rs);
       } else {
-        sa += (double)xv;
-        sb += (double)xv * (double)xv;
+        const double d = (double)xv - shift;
+        sa += d;
+        sb += d * d;
       }
     }
   }
@@ -63,7 +68,8 @@ __global__ void bn_partial_kernel(const float* __restrict__ x, long ldx, const f
 
 // batch statistics of a training-mode forward (torch.nn.functional.batch_norm, training=True): the biased variance
 // normalises, the unbiased one feeds running_var; running <- (1 - momentum) * running + momentum * batch
-__global__ void bn_stats_finish_kernel(const double* __restrict__ parts, int chunks, int batch, int n, float eps,
+__global__ void bn_stats_finish_kernel(const double* __restrict__ parts, const float* __restrict__ x0 /*row 0 of x: the shift*/,
+                                       int chunks, int batch, int n, float eps,
                                        float momentum, int updates, float* __restrict__ save_mean,
                                        float* __restrict__ save_rstd,
                                        float* __restrict__ running_mean, float* __restrict__ running_var) {
@@ -74,8 +80,8 @@ __global__ void bn_stats_finish_kernel(const double* __restrict__ parts, int chu
     s += parts[((long)k * 2 + 0) * n + c];
     q += parts[((long)k * 2 + 1) * n + c];
   }
-  const double mean = s / (double)batch;
-  double var = q / (double)batch - mean * mean;
+  const double ms = s / (double)batch, mean = (double)x0[c] + ms;
+  double var = q / (double)batch - ms * ms;
   if (var < 0.0) var = 0.0;
   save_mean[c] = (float)mean;
   save_rstd[c] = (float)(1.0 / sqrt(var + (double)eps));
@@ -199,7 +205,7 @@ int rg_batch_norm_forward(const float* x, int64_t ldx, const float* gamma, const
     RG_LAUNCH((bn_partial_kernel<false>), dim3((n + BN_COLS - 1) / BN_COLS, chunks), dim3(64 * BN_WAVES), s, x, (long)ldx,
               (const float*)nullptr, 0L, (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, 0.f, batch,
               n, parts);
-    RG_LAUNCH(bn_stats_finish_kernel, dim3((n + 255) / 256), dim3(256), s, (const double*)parts, chunks, batch, n, (float)eps,
+    RG_LAUNCH(bn_stats_finish_kernel, dim3((n + 255) / 256), dim3(256), s, (const double*)parts, x, chunks, batch, n, (float)eps,
               (float)momentum, stat_updates, save_mean, save_rstd, running_mean, running_var);
     RG_LAUNCH(bn_apply_kernel, dim3(sweep_blocks((long)batch * n)), dim3(256), s, x, (long)ldx, (const float*)save_mean,
               (const float*)save_rstd, (const float*)nullptr, (float)eps, gamma, beta, batch, n, y, (long)ldy);

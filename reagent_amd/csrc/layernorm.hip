@@ -35,14 +35,18 @@ __global__ void layer_norm_fwd_kernel(const float* __restrict__ z, long ldz, con
     s += v[i];
   }
   const float mean = wave_sum(s) / (float)n;
-  float q = 0.f;
+  // sum (v - mean)^2 with the ROUNDED mean is sum (v - m)^2 + n (m - mean)^2 of the exact one, m: for a row of spread
+  // 1e-4 around 1 a half ulp of the mean is 6 ulp of rstd.  The residual sum e = sum (v - mean) = n (m - mean) takes it out.
+  float q = 0.f, e = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
     const int c = lane + 64 * i;
     const float d = c < n ? v[i] - mean : 0.f;
     q += d * d;
+    e += d;
   }
-  const float rstd = 1.f / sqrtf(wave_sum(q) / (float)n + eps);
+  e = wave_sum(e);
+  const float rstd = 1.f / sqrtf(fmaxf(wave_sum(q) - e * e / (float)n, 0.f) / (float)n + eps);
 #pragma unroll
   for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
     const int c = lane + 64 * i;

@@ -84,6 +84,9 @@ class GeneralFCStack(FCStack):
         B, dev = xc.shape[0], xc.device
         self._ensure_ws(B, dev)
         training = bool(self._training())
+        if training and B == 1 and any(bn is not None for bn in self.bns):
+            # nn.BatchNorm1d refuses a batch of one row in training mode (its variance is no statistic); so does this path
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {list(xc.shape)}")
         if save:
             self._fwd_training = training
         self._calls += 1

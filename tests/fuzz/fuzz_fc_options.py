@@ -1,4 +1,4 @@
-import os, sys, random
+import os, sys, random, traceback
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, ROOT); sys.path.insert(0, ROOT + "/tests")
 import torch
 import emu_backend
@@ -7,6 +7,7 @@ import reagent_amd._lib as L
 from reagent_amd.engine import ensure_slab, grad_views
 from reagent_amd.models import FullyConnectedNetwork
 from test_fc_options import _reference_pass
+import test_norm_kernel_statements as T
 
 # random FullyConnectedNetwork configurations with batch-norm / layer-norm / dropout / residual wrappers in random
 # combinations, training and eval mode: forward, input gradient, every parameter gradient and the running statistics
@@ -16,6 +17,29 @@ cases = int(sys.argv[2]) if len(sys.argv) > 2 else 16
 random.seed(seed)
 acts = ["relu", "tanh", "leaky_relu", "linear", "sigmoid"]
 bad = 0
+
+# the kernels themselves at random shapes — every width up to LN_MAX_PER_LANE * 64, batches around the 4-row workgroups of
+# layer norm and the 256-row chunks of batch norm — through the checks of tests/test_norm_kernel_statements.py: row / column
+# classes planted at known places, NaN-padded strided operands, every output against the float64 statements of
+# tests/norm_refs.py at bounds calibrated on a torch-only pool of that very shape
+for case in range(cases):
+    B, n = random.choice([1, 2, 3, 6, 7, 8, 11, 21, 40]), random.choice([1, 2, 3, 31, 62, 66, 130, 191, 192, 193, 640, 1999, 2046])
+    act, eps = random.choice(T.ACT_NAMES), random.choice([1e-5, 1e-12, 1e-3])
+    Bb, nb = random.choice([2, 4, 5, 100, 254, 258, 511, 514, 769, 1025]), random.choice([1, 2, 5, 62, 66, 127, 128, 130])
+    o = dict(training=random.random() < 0.7, gamma=random.random() < 0.8, beta=random.random() < 0.8, running=random.random() < 0.8,
+             updates=random.choice([0, 1, 1, 2, 3]), momentum=random.choice([0.1, 0.01, 1.0]))
+    for what, call in ((f"layer norm B={B} n={n} {act} eps={eps}", lambda: T.check_ln("cpu", B, n, act, eps)),
+                       (f"batch norm B={Bb} n={nb} {o}", lambda: T.check_bn("cpu", Bb, nb, shift=random.randrange(5), **o)[0])):
+        try:
+            worst = call()
+            print("OK ", what, "worst ratio %.3f (%s)" % max((r, k) for k, r in worst.items()))
+        except Exception:
+            bad += 1
+            print("BAD", what)
+            traceback.print_exc(limit=2)
+    T._LN.clear()
+    T._BN.clear()
+
 for case in range(cases):
     nl = random.randint(1, 4)
     widths = [random.choice([3, 8, 17, 32, 70])]  # (a width-1 layer norm is constant: the batch norm after it divides rounding noise by sqrt(eps))
