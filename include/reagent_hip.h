@@ -59,7 +59,8 @@ int rg_fc_forward(const void* x, int64_t ldx, const void* w, int64_t ldw, const 
 /* dx = (dz · w) ⊙ act'(h_below).  Replaces autograd's AddmmBackward (input grad) +
  * Relu/Tanh/...Backward of the layer below.
  * dz [batch, out] (lddz); wt = w^T [in, out] (ldwt); ht = saved transposed output of the layer
- * below [in, batch] (ldht) or NULL when that "layer" is the network input / linear.
+ * below [in, batch] (ldht) or NULL when that "layer" is the network input / linear.  With ht given,
+ * an act_below outside RG_ACT_LINEAR..RG_ACT_SOFTPLUS is refused (RG_EINVAL), as rg_fc_forward does.
  * Outputs (nullable): dx [batch, in] compute type, dx32 fp32 (lddx), dxt [in, batch] (lddxt). */
 int rg_fc_dgrad(const void* dz, int64_t lddz, const void* wt, int64_t ldwt, const void* ht,
                 int64_t ldht, int act_below, void* dx, float* dx32, int64_t lddx, void* dxt,

@@ -412,7 +412,7 @@ _lib = None
 _lock = threading.Lock()
 
 
-EUNSUPPORTED = -3  # RG_EUNSUPPORTED
+EINVAL, EUNSUPPORTED, EWORKSPACE = -1, -3, -4  # RG_EINVAL, RG_EUNSUPPORTED, RG_EWORKSPACE
 
 
 class ReagentHipError(RuntimeError):

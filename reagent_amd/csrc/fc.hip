@@ -207,6 +207,7 @@ int rg_fc_dgrad(const void* dz, int64_t lddz, const void* wt, int64_t ldwt, cons
                 int64_t lddxt, int batch, int in_features, int out_features, int precision,
                 rg_stream_t stream) {
   if (!dz || !wt || batch < 0 || out_features <= 0 || in_features <= 0) return RG_EINVAL;
+  if (ht && (act_below < 0 || act_below > RG_ACT_SOFTPLUS)) return RG_EINVAL;  // no derivative to mask by (as rg_fc_forward)
   if (batch == 0) return RG_OK;
   if (precision == RG_PREC_F32)
     return fc_dgrad_t<PrecF32>(dz, lddz, wt, ldwt, ht, ldht, act_below, dx, dx32, lddx, dxt, lddxt,
@@ -219,6 +220,7 @@ int rg_fc_dgrad(const void* dz, int64_t lddz, const void* wt, int64_t ldwt, cons
 
 size_t rg_fc_wgrad_workspace_bytes(int out_features, int in_features, int batch, int precision) {
   const int bk = precision == RG_PREC_BF16 ? PrecBF16::BK : PrecF32::BK;
+  if (out_features <= 0 || in_features <= 0) return 0;  // nothing rg_fc_wgrad would accept (and no tiles to divide by)
   if (batch <= 0) batch = 1;
   const WgradPlan p = wgrad_plan(out_features, in_features, batch, bk);
   return (size_t)p.splits * (p.slab + p.bias_slab) * sizeof(float);

@@ -70,7 +70,7 @@ __device__ __forceinline__ float act_grad_from_output(float h, int act) {
     case ACT_LEAKY_RELU: return h > 0.f ? 1.f : 0.01f;
     case ACT_TANH: return 1.f - h * h;
     case ACT_SIGMOID: return h * (1.f - h);
-    case ACT_SOFTPLUS: return 1.f - expf(-h);
+    case ACT_SOFTPLUS: return -expm1f(-h);  // (1 - expf(-h) is 0 below h = 6e-8, where the derivative is h)
     default: return 1.f;
   }
 }
