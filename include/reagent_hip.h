@@ -1671,6 +1671,49 @@ int rg_frechet_rank(const float* scores, int64_t ld_scores, const float* mem, in
                     int mode, uint64_t seed, int seq_len, int tgt_len, int batch, int embed, int64_t* ranked_tgt_out_idx,
                     float* ranked_per_symbol_probs, float* ranked_per_seq_probs, rg_stream_t stream);
 
+/* ---- the n-gram conv tower as a convolution along time (seqconv.hip) -------------------------------------------------------
+ * NGramConvolutionalNetwork (reagent/models/synthetic_reward.py:311-370) runs ConvolutionalNetwork.conv_forward
+ * (reagent/models/convolutional_network.py:79-87: Conv2d -> relu -> MaxPool2d(1) per layer) on the ngram() windows
+ * (synthetic_reward.py:177-205, :359-367).  The first kernel spans the width and the later ones have width 1, so a layer's
+ * output at an absolute position is the same in every window holding it: the tower is computed once per position.  An
+ * activation is fp32 [positions * batch, channels], row position * batch + b, with its own pitch; all arithmetic is exact
+ * fp32 on v_mfma_f32_32x32x2_f32; no atomics, two runs give the same bits, every output element is written.
+ *
+ * rg_seqconv_forward: y[(q, b), co] = relu(bias[co] + sum_dh sum_ci w[co, ci, dh] * in[(q + dh, b), ci]) for q < positions +
+ * 2 * pad - kh + 1, where in = `pad` zero positions, the `positions` given ones, `pad` zero positions (the reference's
+ * ngram_padding; pad = context_size / 2 for the first layer, 0 after it) and row (p, b) of the given ones is x[p * batch + b]
+ * (columns 0 .. cols) | x2[p * batch + b] (cols2 more columns; x2 null with cols2 = 0): layer 0 reads state and action in
+ * place.  w is torch's Conv2d weight, element (co, ci, dh) at w[co * kh * (cols + cols2) + ci * w_chan_stride + dh *
+ * w_tap_stride]: (1, width) for the first layer's [C, 1, kh, width], (kh, 1) for a later [C, C_in, kh, 1].
+ * rg_seqconv_dgrad: dx[(p, b), ci] = sum_dh sum_co w[co, ci, dh] * dz[(p - dh, b), co] for p < out_positions + kh - 1, zero
+ * filled outside dz's positions, where dz = dy masked by y > 0 (y nullable: dy is dz already), and the result masked by
+ * below > 0 (below, nullable: the relu output of the layer underneath, dx's shape).
+ * rg_seqconv_wgrad: dw[co, ci, dh] = sum_m dz[m, co] * in[m + dh * batch, ci] in w's layout and dbias[co] = sum_m dz[m, co];
+ * the rows are split over workgroups, the partials lie in workspace (rg_seqconv_wgrad_workspace_bytes) and a second launch
+ * adds them in split order.
+ * rg_ngram_window: feat[(t, b), c * height + h] = g[(t + h, b), c] for g of seq_len + height - 1 positions (x.view(-1,
+ * fc_input_dim) of the reference's [N, C, H, 1], convolutional_network.py:95).  rg_ngram_window_backward: dg[(p, b), c] =
+ * sum_h dfeat[(p - h, b), c * height + h] over the steps that exist, fp32 adds in ascending h, masked by g > 0 (g nullable).
+ * RG_EINVAL for a width or channel count above RG_SEQCONV_MAX_CHANNELS, kh, height or 2 * pad + 1 above
+ * RG_SEQCONV_MAX_CONTEXT, no output position, a size below 1, positions * batch >= 2^29, a pitch below its row or a missing
+ * pointer; RG_EWORKSPACE for a short workspace. */
+#define RG_SEQCONV_MAX_CHANNELS 512
+#define RG_SEQCONV_MAX_CONTEXT 15
+int rg_seqconv_forward(const float* x, int64_t ldx, const float* x2, int64_t ldx2, int cols, int cols2, int positions, int pad,
+                       int batch, int kh, const float* w, int64_t w_chan_stride, int64_t w_tap_stride, const float* bias,
+                       int out_channels, float* y, int64_t ldy, rg_stream_t stream);
+int rg_seqconv_dgrad(const float* dy, int64_t ld_dy, const float* y, int64_t ldy, int out_positions, int batch, int kh,
+                     const float* w, int64_t w_chan_stride, int64_t w_tap_stride, int in_channels, int out_channels,
+                     const float* below, int64_t ld_below, float* dx, int64_t ld_dx, rg_stream_t stream);
+size_t rg_seqconv_wgrad_workspace_bytes(int out_positions, int batch, int kh, int in_channels, int out_channels);
+int rg_seqconv_wgrad(const float* dz, int64_t ld_dz, const float* x, int64_t ldx, const float* x2, int64_t ldx2, int cols, int cols2,
+                     int positions, int pad, int batch, int kh, int out_channels, int64_t w_chan_stride, int64_t w_tap_stride,
+                     float* dw, float* dbias, void* workspace, size_t workspace_bytes, rg_stream_t stream);
+int rg_ngram_window(const float* g, int64_t ldg, int seq_len, int batch, int channels, int height, float* feat, int64_t ld_feat,
+                    rg_stream_t stream);
+int rg_ngram_window_backward(const float* dfeat, int64_t ld_dfeat, const float* g, int64_t ldg, int seq_len, int batch, int channels,
+                             int height, float* dg, int64_t ld_dg, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

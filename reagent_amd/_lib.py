@@ -29,6 +29,8 @@ LINUCB_SOLVE_MAX_DIM = 128  # RG_LINUCB_SOLVE_MAX_DIM: rg_linucb_solve's limit (
 LSTM_MAX_HIDDEN, LSTM_MAX_LAYERS = 256, 4  # RG_LSTM_MAX_HIDDEN, RG_LSTM_MAX_LAYERS: the LSTM kernels' limits
 ATTN_MAX_SEQ_LEN, ATTN_MAX_HEAD_DIM, ATTN_MAX_EMBED = 64, 128, 512  # RG_ATTN_MAX_*: the attention kernels' limits
 S2S_MAX_SEQ_LEN, S2S_MAX_EMBED = 64, 512  # RG_S2S_MAX_*: the Seq2Slate kernels' limits (a lane per candidate)
+SEQCONV_MAX_CHANNELS, SEQCONV_MAX_CONTEXT = 512, 15  # RG_SEQCONV_MAX_*: the sequence-convolution kernels' limits
+SEQCONV_MAX_LAYERS = 4  # conv layers of an NGramConvolutionalNetwork (a host limit: each layer is a launch)
 IPS_CLAMP_NONE, IPS_CLAMP_UNIVERSAL, IPS_CLAMP_AGGRESSIVE = 0, 1, 2  # RG_IPS_CLAMP_*: rg_frechet_head's clamp methods
 FRECHET_RANK_ENCODER, FRECHET_RANK_GREEDY, FRECHET_RANK_SAMPLED = 0, 1, 2  # RG_FRECHET_RANK_*: rg_frechet_rank's modes
 MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
@@ -406,6 +408,14 @@ SIGNATURES = {
                         + [c_int] * 4 + [c_void_p] * 5 + [c_void_p, c_i64] * 2 + [c_void_p] * 3 + [c_void_p]),
     "rg_frechet_rank": (c_int, [c_void_p, c_i64] * 2 + [c_void_p, c_void_p, c_int, ctypes.c_uint64] + [c_int] * 4
                         + [c_void_p] * 3 + [c_void_p]),
+    "rg_seqconv_forward": (c_int, [c_void_p, c_i64] * 2 + [c_int] * 6 + [c_void_p, c_i64, c_i64, c_void_p, c_int, c_void_p, c_i64,
+                                                                         c_void_p]),
+    "rg_seqconv_dgrad": (c_int, [c_void_p, c_i64] * 2 + [c_int] * 3 + [c_void_p, c_i64, c_i64, c_int, c_int]
+                         + [c_void_p, c_i64] * 2 + [c_void_p]),
+    "rg_seqconv_wgrad_workspace_bytes": (c_sz, [c_int] * 5),
+    "rg_seqconv_wgrad": (c_int, [c_void_p, c_i64] * 3 + [c_int] * 7 + [c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_sz, c_void_p]),
+    "rg_ngram_window": (c_int, [c_void_p, c_i64] + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
+    "rg_ngram_window_backward": (c_int, [c_void_p, c_i64] * 2 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
 }
 
 _lib = None

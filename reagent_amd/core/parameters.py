@@ -87,6 +87,17 @@ class EvaluationParameters:
 
 
 @dataclass(frozen=True)
+class ConvNetParameters:
+    """reagent/core/parameters.py:170-176: the conv tower of NGramConvolutionalNetwork (conv_width_kernels is set by the net)"""
+
+    conv_dims: List[int]
+    conv_height_kernels: List[int]
+    pool_types: List[str]
+    pool_kernel_sizes: List[int]
+    conv_width_kernels: Optional[List[int]] = None
+
+
+@dataclass(frozen=True)
 class NormalizationParameters:
     feature_type: str
     boxcox_lambda: Optional[float] = None

@@ -19,5 +19,6 @@ from .synthetic_reward import (  # noqa: F401
     SingleStepSyntheticRewardNet,
     SyntheticRewardNet,
 )
+from .synthetic_reward_conv import NGramConvolutionalNetwork  # noqa: F401
 from .synthetic_reward_transformer import TransformerSyntheticRewardNet  # noqa: F401
 from .seq2slate import BaselineNet, Seq2SlateTransformerNet, Seq2SlateTransformerOutput  # noqa: F401

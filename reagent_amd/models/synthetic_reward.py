@@ -23,8 +23,8 @@ _gen_mask asserts on the host.
 
 Refused by name: lstm_bidirectional, lstm_hidden_size > 256, lstm_num_layers > 4 (the LSTM kernels' limits), an even
 context_size, an activation outside the six HIP epilogues, use_batch_norm on the single-step net (its BatchNorm1d would see
-3-D input).  TransformerSyntheticRewardNet is its own module, models/synthetic_reward_transformer.py (re-exported from
-reagent_amd.models, not from here).  Not built: NGramConvolutionalNetwork.
+3-D input).  TransformerSyntheticRewardNet and NGramConvolutionalNetwork are modules of their own,
+models/synthetic_reward_transformer.py and models/synthetic_reward_conv.py (re-exported from reagent_amd.models, not from here).
 
 ngram and _gen_mask are plain torch statements of the reference's functions: the tests compare the kernels against them.
 """
@@ -298,8 +298,8 @@ class SyntheticRewardNet(ModelBase):
         super().__init__()
         if not isinstance(net, _RewardTrunk):
             raise NotImplementedError("SyntheticRewardNet: net must be a reagent_amd SingleStepSyntheticRewardNet, "
-                                      f"NGramFullyConnectedNetwork or SequenceSyntheticRewardNet (got {type(net).__name__}): the "
-                                      "head runs behind their trunks")
+                                      "NGramFullyConnectedNetwork, NGramConvolutionalNetwork, SequenceSyntheticRewardNet or "
+                                      f"TransformerSyntheticRewardNet (got {type(net).__name__}): the head runs behind their trunks")
         self.net = net
 
     @staticmethod

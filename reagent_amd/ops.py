@@ -2120,3 +2120,110 @@ def frechet_rank(mode: int, seq_len: int, batch: int, ranked_tgt_out_idx, ranked
          lambda: L.lib().rg_frechet_rank(L.ptr(scores), ld_s, L.ptr(mem), ld_m, L.ptr(w), L.ptr(bias), int(mode),
                                          int(seed) & 0xFFFFFFFFFFFFFFFF, S, T, B, E, L.ptr(ranked_tgt_out_idx),
                                          L.ptr(ranked_per_symbol_probs), L.ptr(ranked_per_seq_probs), L.stream_ptr()))
+
+
+# ---- the n-gram conv tower as a convolution along time (seqconv.hip) -----------------------------------------------------------
+def _seqconv_check(who: str, cin: int, cout: int, kh: int, pad: int = 0):
+    C, K = L.SEQCONV_MAX_CHANNELS, L.SEQCONV_MAX_CONTEXT
+    if not 1 <= cin <= C or not 1 <= cout <= C:
+        raise NotImplementedError(f"{who}: {cin} input and {cout} output channels are not supported (1 .. {C} each)")
+    if not 1 <= kh <= K or not 0 <= 2 * pad + 1 <= K:
+        raise NotImplementedError(f"{who}: a height kernel of {kh} with a context of {2 * pad + 1} is not supported (1 .. {K})")
+
+
+def _seqconv_input(x, x2, positions: int, batch: int):
+    """(x pointer, pitch, x2 pointer, pitch, cols, cols2) of a layer's input rows: [positions * batch, cols] (| cols2 of x2)"""
+    ld = _rows_f32(x, positions * batch, x.shape[1], "x")
+    if x2 is None:
+        return L.ptr(x), ld, None, 0, x.shape[1], 0
+    return L.ptr(x), ld, L.ptr(x2), _rows_f32(x2, positions * batch, x2.shape[1], "x2"), x.shape[1], x2.shape[1]
+
+
+def _conv_weight(w, cin: int, kh: int):
+    """(channel stride, tap stride) of a contiguous Conv2d weight: [C, 1, kh, cin] (the first layer) or [C, cin, kh, 1]"""
+    assert w.dtype == F32 and w.is_contiguous() and w.dim() == 4, (w.dtype, w.shape)
+    if tuple(w.shape[1:]) == (1, kh, cin):
+        return 1, cin
+    assert tuple(w.shape[1:]) == (cin, kh, 1), (w.shape, cin, kh)
+    return kh, 1
+
+
+def seqconv_forward(x, x2, positions: int, pad: int, batch: int, w, bias, y):
+    """y [(positions + 2 pad - kh + 1) * batch, C] = relu(conv along time of (x | x2) with `pad` zero positions on either side)
+    (see rg_seqconv_forward); x [positions * batch, cols], x2 (optional) [positions * batch, cols2], w a Conv2d weight"""
+    _chk_dev(x, x2, w, bias, y)
+    xp, ldx, x2p, ldx2, cols, cols2 = _seqconv_input(x, x2, positions, batch)
+    cout, kh = w.shape[0], w.shape[2]
+    _seqconv_check("seqconv_forward", cols + cols2, cout, kh, pad)
+    cs, ts = _conv_weight(w, cols + cols2, kh)
+    p_out = positions + 2 * pad - kh + 1
+    ldy = _rows_f32(y, p_out * batch, cout, "y")
+    _run("rg_seqconv_forward", dict(M=p_out * batch, N=cout, K=kh * (cols + cols2)),
+         lambda: L.lib().rg_seqconv_forward(xp, ldx, x2p, ldx2, cols, cols2, positions, pad, batch, kh, L.ptr(w), cs, ts, L.ptr(bias),
+                                            cout, L.ptr(y), ldy, L.stream_ptr()))
+
+
+def seqconv_dgrad(dy, out_positions: int, batch: int, w, dx, y=None, below=None):
+    """dx [(out_positions + kh - 1) * batch, C_in] from d loss / d the layer's output dy [out_positions * batch, C_out]; y
+    (optional): the layer's relu output, whose mask dy takes on load; below (optional): the relu output of the layer
+    underneath, whose mask dx takes (see rg_seqconv_dgrad)"""
+    _chk_dev(dy, w, dx, y, below)
+    cout, cin, kh = w.shape[0], dx.shape[1], w.shape[2]
+    _seqconv_check("seqconv_dgrad", cin, cout, kh)
+    cs, ts = _conv_weight(w, cin, kh)
+    rows = (out_positions + kh - 1) * batch
+    ld_dy, ld_dx = _rows_f32(dy, out_positions * batch, cout, "dy"), _rows_f32(dx, rows, cin, "dx")
+    ldy = _rows_f32(y, out_positions * batch, cout, "y") if y is not None else 0
+    ldb = _rows_f32(below, rows, cin, "below") if below is not None else 0
+    _run("rg_seqconv_dgrad", dict(M=rows, N=cin, K=kh * cout),
+         lambda: L.lib().rg_seqconv_dgrad(L.ptr(dy), ld_dy, L.ptr(y), ldy, out_positions, batch, kh, L.ptr(w), cs, ts, cin, cout,
+                                          L.ptr(below), ldb, L.ptr(dx), ld_dx, L.stream_ptr()))
+
+
+def seqconv_wgrad_workspace_bytes(out_positions: int, batch: int, kh: int, cin: int, cout: int) -> int:
+    return int(L.lib().rg_seqconv_wgrad_workspace_bytes(out_positions, batch, kh, cin, cout))
+
+
+def seqconv_wgrad(dz, x, x2, positions: int, pad: int, batch: int, dw, dbias, workspace):
+    """dw (a contiguous Conv2d weight gradient) and dbias [C_out] from dz [(positions + 2 pad - kh + 1) * batch, C_out] and the
+    layer's input as seqconv_forward takes it (see rg_seqconv_wgrad)"""
+    _chk_dev(dz, x, x2, dw, dbias, workspace)
+    xp, ldx, x2p, ldx2, cols, cols2 = _seqconv_input(x, x2, positions, batch)
+    cout, kh = dw.shape[0], dw.shape[2]
+    _seqconv_check("seqconv_wgrad", cols + cols2, cout, kh, pad)
+    cs, ts = _conv_weight(dw, cols + cols2, kh)
+    ld_dz = _rows_f32(dz, (positions + 2 * pad - kh + 1) * batch, cout, "dz")
+    _f32_flat(dbias, cout)
+    _run("rg_seqconv_wgrad", dict(M=cout, N=kh * (cols + cols2), K=dz.shape[0]),
+         lambda: L.lib().rg_seqconv_wgrad(L.ptr(dz), ld_dz, xp, ldx, x2p, ldx2, cols, cols2, positions, pad, batch, kh, cout, cs, ts,
+                                          L.ptr(dw), L.ptr(dbias), L.ptr(workspace), workspace.numel() * workspace.element_size(),
+                                          L.stream_ptr()))
+
+
+def _window_check(who: str, C: int, H: int):
+    if not 1 <= C <= L.SEQCONV_MAX_CHANNELS or not 1 <= H <= L.SEQCONV_MAX_CONTEXT:
+        raise NotImplementedError(f"{who}: {C} channels of height {H} are not supported (1 .. {L.SEQCONV_MAX_CHANNELS} channels, "
+                                  f"height 1 .. {L.SEQCONV_MAX_CONTEXT})")
+
+
+def ngram_window(g, seq_len: int, batch: int, height: int, feat):
+    """feat [T * B, C * H], column c * H + h of row (t, b) = g[(t + h, b), c] (see rg_ngram_window); g [(T + H - 1) * B, C]"""
+    _chk_dev(g, feat)
+    T, B, H, C = int(seq_len), int(batch), int(height), g.shape[1]
+    _window_check("ngram_window", C, H)
+    ldg, ldf = _rows_f32(g, (T + H - 1) * B, C, "g"), _rows_f32(feat, T * B, C * H, "feat")
+    _run("rg_ngram_window", dict(T=T, B=B, C=C, H=H),
+         lambda: L.lib().rg_ngram_window(L.ptr(g), ldg, T, B, C, H, L.ptr(feat), ldf, L.stream_ptr()))
+
+
+def ngram_window_backward(dfeat, seq_len: int, batch: int, height: int, dg, g=None):
+    """dg [(T + H - 1) * B, C] = the gather's reverse of dfeat [T * B, C * H], masked where g (optional, the tower's relu
+    output) is not positive (see rg_ngram_window_backward)"""
+    _chk_dev(dfeat, dg, g)
+    T, B, H, C = int(seq_len), int(batch), int(height), dg.shape[1]
+    _window_check("ngram_window_backward", C, H)
+    rows = (T + H - 1) * B
+    ldf, ldd = _rows_f32(dfeat, T * B, C * H, "dfeat"), _rows_f32(dg, rows, C, "dg")
+    ldg = _rows_f32(g, rows, C, "g") if g is not None else 0
+    _run("rg_ngram_window_backward", dict(T=T, B=B, C=C, H=H),
+         lambda: L.lib().rg_ngram_window_backward(L.ptr(dfeat), ldf, L.ptr(g), ldg, T, B, C, H, L.ptr(dg), ldd, L.stream_ptr()))
