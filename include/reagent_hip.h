@@ -1714,6 +1714,24 @@ int rg_ngram_window(const float* g, int64_t ldg, int seq_len, int batch, int cha
 int rg_ngram_window_backward(const float* dfeat, int64_t ld_dfeat, const float* g, int64_t ldg, int seq_len, int batch, int channels,
                              int height, float* dg, int64_t ld_dg, rg_stream_t stream);
 
+/* ---- the weight gradient from row-major operands over many rows (fc_rows.hip) ----------------------------------------------
+ * dw[o, i] = sum_n dz[n, o] * x[n, i], written contiguous [out, in], and db[o] = sum_n dz[n, o] (db nullable).  Replaces
+ * torch.nn.Linear's backward (autograd's AddmmBackward: grad_weight = grad_output^T . input, grad_bias = grad_output.sum(0))
+ * for the linear layers of the sequence nets, whose dz [rows, out] (ld_dz) and x [rows, in] (ldx) lie row-major: rg_fc_wgrad
+ * takes the TRANSPOSED copies and so costs its callers two rg_transpose_cast launches first.  fp32 only, exact fp32
+ * products and sums on v_mfma_f32_32x32x2_f32.  The rows are split over workgroups, splits x tiles near the CU count; rows
+ * per split are a multiple of RG_FC_ROWS_SLAB, so RG_FC_ROWS_SLAB rows or fewer are always one split.  With one split dw
+ * and db are written by the one launch and no workspace is read (the query returns 0); with more the partials lie in
+ * workspace, splits * (out * in + out) floats, and a second launch adds them in ascending split order.  No atomics, two runs
+ * give the same bits, every output element is written and nothing outside dw, db and the workspace's queried bytes.
+ * RG_EINVAL for a missing dz, x or dw, a size below 1, a width above RG_FC_ROWS_MAX_WIDTH or a pitch below its row;
+ * RG_EWORKSPACE for a missing or short workspace where one is needed.  The query returns 0 for anything the call refuses. */
+#define RG_FC_ROWS_MAX_WIDTH 512
+#define RG_FC_ROWS_SLAB 32
+size_t rg_fc_wgrad_rows_workspace_bytes(int out_features, int in_features, int rows);
+int rg_fc_wgrad_rows(const float* dz, int64_t ld_dz, const float* x, int64_t ldx, float* dw, float* db, void* workspace,
+                     size_t workspace_bytes, int out_features, int in_features, int rows, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,5 +62,5 @@ def linear_backward(cache, dz, x_in, name, w, dw, db, rows=slice(None), need_dx=
     if need_dx:
         dx = torch.empty(N, w.shape[1], dtype=F32, device=dz.device)
         ops.fc_dgrad(dz, cache(name, w, rows), None, L.ACT["linear"], L.PREC_F32, dx32=dx)
-    lstm_stack.wgrad(lstm_stack.transposed(dz), lstm_stack.transposed(x_in), dw[rows], db[rows], N)
+    lstm_stack.wgrad_rows(dz, x_in, dw[rows], db[rows])
     return dx

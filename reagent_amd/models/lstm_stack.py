@@ -4,8 +4,9 @@ _Parameters holder of nn.LSTM's parameters under torch's own names (weight_ih_l0
 their state_dict keys stay rnn.weight_ih_l0 ...
 
   forward : per layer rg_fc_forward (x W_ih^T + b_ih of all steps at once) and rg_lstm_forward (the recurrence)
-  backward: per layer, from the top, rg_lstm_backward, dW_ih and db_ih = rg_fc_wgrad(dgates, x), dW_hh and db_hh =
-            rg_fc_wgrad(dgates, [h0; h_all[:-1]]), dx = rg_fc_dgrad(dgates, W_ih)
+  backward: per layer, from the top, rg_lstm_backward, dW_ih and db_ih = wgrad_rows(dgates, x), dW_hh and db_hh =
+            wgrad_rows(dgates, [h0; h_all[:-1]]), dx = rg_fc_dgrad(dgates, W_ih); wgrad_rows is rg_fc_wgrad_rows on the
+            row-major operands from WGRAD_ROWS_MIN rows on, two rg_transpose_cast and rg_fc_wgrad below
 
 A layer's initial hidden state is row k of an [L, B, H] tensor (MDNRNN's `hidden`) or one [B, H] tensor that every layer
 starts from (Seq2RewardNetwork's embedding); its initial cell is row k of an [L, B, H] tensor or zero.
@@ -19,6 +20,11 @@ from ..engine import _mat
 
 F32 = torch.float32
 LINEAR = L.ACT["linear"]
+# rows from which wgrad_rows takes rg_fc_wgrad_rows.  On the MI355X it beat two rg_transpose_cast + rg_fc_wgrad at 128 x 128
+# at every row count measured, from 32 up (profiles/NOTES_r33.md); 256 is the smallest power of two above the 132 rows that
+# the suite's recorded replays send through the path they were recorded against
+WGRAD_ROWS_MIN = 256
+WGRAD_ROWS_MAX_WIDTH = 512  # RG_FC_ROWS_MAX_WIDTH
 
 
 class _Parameters(nn.Module):
@@ -73,6 +79,22 @@ def wgrad(dzt, xt, w_grad, b_grad, rows):
     ops.fc_wgrad(dzt, xt, w_grad, b_grad, ws, L.PREC_F32)
 
 
+def wgrad_rows(dz, x, w_grad, b_grad, dzt=None):
+    """dW and db of a linear layer from the row-major d loss / d output dz [rows, out] and input x [rows, in].  From
+    WGRAD_ROWS_MIN rows on (widths rg_fc_wgrad_rows takes, fp32, unit column stride) one rg_fc_wgrad_rows on the operands
+    as they lie; below it two transposes and rg_fc_wgrad, as before the row-major kernel existed.  -> dz's transposed copy
+    where that path made or took one (dzt: a caller with two layers on one dz hands the first call's on), else None"""
+    rows = dz.shape[0]
+    widths_ok = max(dz.shape[1], x.shape[1]) <= WGRAD_ROWS_MAX_WIDTH
+    if rows < WGRAD_ROWS_MIN or not widths_ok or dz.dtype != F32 or x.dtype != F32 or dz.stride(1) != 1 or x.stride(1) != 1:
+        dzt = transposed(dz) if dzt is None else dzt
+        wgrad(dzt, transposed(x), w_grad, b_grad, rows)
+        return dzt
+    nbytes = ops.fc_wgrad_rows_workspace_bytes(dz.shape[1], x.shape[1], rows)
+    ws = torch.empty((nbytes + 15) // 16 * 4, dtype=F32, device=dz.device) if nbytes else None
+    ops.fc_wgrad_rows(dz, x, w_grad, b_grad, ws)
+
+
 def forward(rnn, x, T, B, H, layers, h0=None, c0=None, save=False):
     """the stack over x [T * B, In] -> the tape entries dict(x, h, c, gates): per layer the input rows, h_all and c_all
     [T, B, H] and (save) the gates [T, B, 4 H], else None"""
@@ -109,11 +131,10 @@ def backward(rnn, tape, dh_top, grad, h0, c0, transposed_weight, want_dh0):
             dh0[k] = torch.empty(B, H, **f)
         ops.lstm_backward(dh.view(T, B, H), tape["gates"][k], tape["c"][k], _initial(c0, k), w_hh.detach(), dgates, dh0[k])
         dg = dgates.view(N, 4 * H)
-        dgt = transposed(dg)
-        wgrad(dgt, transposed(tape["x"][k]), grad[id(w_ih)], grad[id(b_ih)], N)
+        dgt = wgrad_rows(dg, tape["x"][k], grad[id(w_ih)], grad[id(b_ih)])
         first = h0_k.unsqueeze(0) if h0_k is not None else torch.zeros(1, B, H, **f)
         h_prev = torch.cat([first, tape["h"][k][:-1]], dim=0).view(N, H)
-        wgrad(dgt, transposed(h_prev), grad[id(w_hh)], grad[id(b_hh)], N)
+        wgrad_rows(dg, h_prev, grad[id(w_hh)], grad[id(b_hh)], dzt=dgt)
         if k > 0:
             dh = torch.empty(N, H, **f)
             ops.fc_dgrad(dg, transposed_weight(f"ih{k}", w_ih), None, LINEAR, L.PREC_F32, dx32=dh)

@@ -112,9 +112,8 @@ class MDNRNN(nn.Module):
         T, B, H = tape["T"], tape["B"], self.num_hiddens
         N, dev = T * B, dz.device
         f = dict(dtype=F32, device=dev)
-        transposed = lstm_stack.transposed
         gw, gb = self.gmm_linear.weight, self.gmm_linear.bias
-        lstm_stack.wgrad(transposed(dz), transposed(tape["h"][-1].view(N, H)), grad[id(gw)], grad[id(gb)], N)
+        lstm_stack.wgrad_rows(dz, tape["h"][-1].view(N, H), grad[id(gw)], grad[id(gb)])
         dh = torch.empty(N, H, **f)
         ops.fc_dgrad(dz, self._wt("gmm", gw), None, LINEAR, L.PREC_F32, dx32=dh)
         lstm_stack.backward(self.rnn, tape, dh, grad, tape["h0"], tape["c0"], self._wt, want_dh0=False)

@@ -172,6 +172,5 @@ class Seq2RewardNetwork(ModelBase):
         for k in range(1, self.num_hidden_layers):
             demb = demb + dh0[k]
         gw, gb = self.map_linear.weight, self.map_linear.bias
-        lstm_stack.wgrad(lstm_stack.transposed(demb), lstm_stack.transposed(tape["state0"]), grad[id(gw)], grad[id(gb)],
-                         tape["B"])
+        lstm_stack.wgrad_rows(demb, tape["state0"], grad[id(gw)], grad[id(gb)])
         return slab

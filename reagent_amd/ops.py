@@ -144,6 +144,24 @@ def fc_wgrad(dzt, xt, dw, db, workspace, precision: int):
                                      in_f, batch, precision, L.stream_ptr()))
 
 
+def fc_wgrad_rows_workspace_bytes(out_f, in_f, rows) -> int:
+    return int(L.lib().rg_fc_wgrad_rows_workspace_bytes(out_f, in_f, rows))
+
+
+def fc_wgrad_rows(dz, x, dw, db, workspace):
+    """dw[out,in] (contiguous fp32) = dz^T x, db[out] = sum_n dz (nullable) from the ROW-MAJOR fp32 dz [rows, out] and
+    x [rows, in] (unit column stride, any row pitch); workspace of fc_wgrad_rows_workspace_bytes (None where that is 0)."""
+    _chk_dev(dz, x, dw, db, workspace)
+    rows, out_f = dz.shape
+    in_f = x.shape[1]
+    assert x.shape[0] == rows and dz.dtype == x.dtype == F32
+    assert dw.is_contiguous() and dw.dtype == F32 and dw.shape == (out_f, in_f)
+    nbytes = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    _run("rg_fc_wgrad_rows", dict(M=out_f, N=in_f, K=rows),
+         lambda: L.lib().rg_fc_wgrad_rows(L.ptr(dz), _ld(dz), L.ptr(x), _ld(x), L.ptr(dw), L.ptr(db), L.ptr(workspace),
+                                          nbytes, out_f, in_f, rows, L.stream_ptr()))
+
+
 def act_backward(dy, y, act: int, dz):
     """dz = dy * act'(z) through the activation output y (all fp32 [rows, cols], unit column stride)"""
     _chk_dev(dy, y, dz)
