@@ -1361,6 +1361,59 @@ int rg_step_ce_head_partials(int batch);
 int rg_step_ce_head(const float* logits, const int64_t* valid_step, int batch, int classes, float* dlogits, float* softmax,
                     double* partials, float* loss, rg_stream_t stream);
 
+/* World model: the evaluators (reagent/evaluation/world_model_evaluator.py).  Additive symbols: the ABI number does not
+ * move.  All fp32; no atomics anywhere: two runs give the same bits.  A table of blocks is int32 [count][2] = (start, end)
+ * in device memory; a block is at most RG_WM_MAX_BLOCK columns wide.  The cap is the widest input the MDN-RNN accepts
+ * (state_dim + action_dim <= RG_MDN_MAX_STATE_DIM), so every feature block and every discrete action vector of a network
+ * that exists is admitted; at H = 256 the ablation kernel's LDS is then two 32 x 257 images and one 32 x 513: 128.4 KB.
+ *
+ * rg_wm_feature_fill: the replacement value of every block over the rows x [n, width] (pitch ldx): fill [width], written
+ * at the blocks' columns only.  A block one column wide gets the column's mean (accumulated in double in a fixed order,
+ * rounded once: the reference takes it in fp32).  A wider block is a one-hot enum and follows compute_median_feature_value
+ * (:159-173): the column sums, their lower median (torch.median), 1 at the first column whose sum equals it, 0 elsewhere.
+ *
+ * rg_lstm_forward_ablate: layer 0 of the LSTM over variants x batch virtual rows, all seq_len steps in one launch, grid
+ * (ceil(batch / 32), variants).  Variant v is blocks[v] = (start, end) with the replacement values fill[v * fill_stride +
+ * c] for c in [start, end) (fill_stride = 0: one [input_width] vector for all, as rg_wm_feature_fill writes it; fill_stride
+ * = A with fill the A x A identity and every block [0, A): the discrete-action sweep, variant i = "every action is i").
+ * Row (v, b) at step t reads the SHARED xproj[t, b] (= x W_ih^T + b_ih of the unablated rows x [seq_len * batch,
+ * input_width], pitch ldx) and adds sum_c (fill_c - x[t, b, c]) * w_ih[g H + u, c], an fp32 MFMA chain in k order over the
+ * block (every width takes it) whose deltas are staged in LDS per step; w_ih [4H, input_width].  Everything else is
+ * rg_lstm_forward's (tile, k-ordered recurrence, gates in double) from the zero state (h0 = c0 = NULL there; b_hh
+ * nullable).  Outputs h_all, c_all [seq_len, variants, batch, H]; no gates (no backward).  A variant whose deltas are all
+ * zero (an empty block, a fill equal to the data) gives rg_lstm_forward's bits.  max_width >= every block's width sizes
+ * the delta image.
+ *
+ * rg_wm_mdn_losses: rg_mdn_head's four losses for every variant, without dz: z [seq_len * variants * batch, .] (pitch ldz)
+ * with row (t, v, b), the UNREPLICATED targets read at row t * batch + b, first_row as rg_mdn_head's (< seq_len * batch).
+ * losses [variants, 4]; partials: 3 * rg_wm_mdn_losses_partials(seq_len, batch, variants) doubles.  The rows of a
+ * workgroup and the order of every sum are rg_mdn_head's: variant v's four floats are the bits rg_mdn_head gives on that
+ * variant's rows gathered.
+ *
+ * rg_wm_mus_sensitivity: sensitivity[f] = the mean over rows and gaussians of sum_{c in block f} |z_shuffled[r, g S + c] -
+ * z[r, g S + c]| (the mus are the first G * S columns of gmm_linear's output; :219-237), in double in a fixed order,
+ * rounded once.  blocks index the state vector; partials: rg_wm_mus_sensitivity_partials(n, num_blocks) doubles.
+ *
+ * All: RG_EINVAL for a count < 1, a null pointer not marked nullable, a pitch below the row; RG_EUNSUPPORTED for hidden >
+ * RG_LSTM_MAX_HIDDEN, max_width > RG_WM_MAX_BLOCK, more than 65535 variants or blocks, seq_len * batch * variants >= 2^29,
+ * num_gaussians > RG_MDN_MAX_GAUSSIANS or state_dim > RG_MDN_MAX_STATE_DIM.  Block bounds are the host's to check (the
+ * kernels clamp them into the row). */
+#define RG_WM_MAX_BLOCK 512
+int rg_wm_feature_fill(const float* x, int64_t ldx, int n, int width, const int32_t* blocks, int num_blocks, float* fill,
+                       rg_stream_t stream);
+int rg_lstm_forward_ablate(const float* xproj, const float* x, int64_t ldx, const float* w_ih, const float* w_hh,
+                           const float* b_hh, const int32_t* blocks, const float* fill,
+                           int64_t fill_stride, int max_width, int seq_len, int batch, int hidden, int input_width, int variants,
+                           float* h_all, float* c_all, rg_stream_t stream);
+int rg_wm_mdn_losses_partials(int seq_len, int batch, int variants);
+int rg_wm_mdn_losses(const float* z, int64_t ldz, const float* next_state, const float* reward, const float* not_terminal,
+                     double next_state_loss_weight, double not_terminal_loss_weight, double reward_loss_weight,
+                     int divide_by_state_dim, int first_row, int seq_len, int batch, int variants, int num_gaussians,
+                     int state_dim, double* partials, float* losses, rg_stream_t stream);
+int rg_wm_mus_sensitivity_partials(int n, int num_blocks);
+int rg_wm_mus_sensitivity(const float* z, const float* z_shuffled, int64_t ldz, int n, int num_gaussians, int state_dim,
+                          const int32_t* blocks, int num_blocks, double* partials, float* sensitivity, rg_stream_t stream);
+
 /* World model: the cross-entropy-method planner (reagent/models/cem_planner.py).  Additive symbols: the ABI number does not
  * move.  Everything is on the caller's stream; no atomics, no flag a workgroup waits on: two runs give the same bits.
  *

@@ -34,6 +34,7 @@ SEQCONV_MAX_LAYERS = 4  # conv layers of an NGramConvolutionalNetwork (a host li
 IPS_CLAMP_NONE, IPS_CLAMP_UNIVERSAL, IPS_CLAMP_AGGRESSIVE = 0, 1, 2  # RG_IPS_CLAMP_*: rg_frechet_head's clamp methods
 FRECHET_RANK_ENCODER, FRECHET_RANK_GREEDY, FRECHET_RANK_SAMPLED = 0, 1, 2  # RG_FRECHET_RANK_*: rg_frechet_rank's modes
 MDN_MAX_GAUSSIANS, MDN_MAX_STATE_DIM = 32, 512  # RG_MDN_MAX_*: rg_mdn_head's limits
+WM_MAX_BLOCK = 512  # RG_WM_MAX_BLOCK: the widest feature block of the world-model evaluators' kernels
 STEP_CE_MAX_CLASSES = 32  # RG_STEP_CE_MAX_CLASSES: rg_step_ce_head's limit (Seq2Reward's multi_steps)
 CEM_MAX_MODELS, CEM_MAX_HORIZON, CEM_MAX_INPUT = 16, 64, 512  # RG_CEM_MAX_*: the CEM planner kernels' limits
 CEM_MAX_TRAJECTORIES = 1 << 20  # RG_CEM_MAX_TRAJECTORIES: population * ensemble stays below it
@@ -377,6 +378,15 @@ SIGNATURES = {
     "rg_seq2reward_head": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_void_p] * 6 + [c_void_p]),
     "rg_step_ce_head_partials": (c_int, [c_int]),
     "rg_step_ce_head": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4 + [c_void_p]),
+    "rg_wm_feature_fill": (c_int, [c_void_p, c_i64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "rg_lstm_forward_ablate": (c_int, [c_void_p, c_void_p, c_i64] + [c_void_p] * 5 + [c_i64] + [c_int] * 6
+                               + [c_void_p] * 2 + [c_void_p]),
+    "rg_wm_mdn_losses_partials": (c_int, [c_int] * 3),
+    "rg_wm_mdn_losses": (c_int, [c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_d, c_d, c_d] + [c_int] * 7
+                         + [c_void_p] * 2 + [c_void_p]),
+    "rg_wm_mus_sensitivity_partials": (c_int, [c_int] * 2),
+    "rg_wm_mus_sensitivity": (c_int, [c_void_p, c_void_p, c_i64] + [c_int] * 3 + [c_void_p, c_int] + [c_void_p] * 2
+                              + [c_void_p]),
     "rg_cem_fill_noise": (c_int, [ctypes.c_uint64] + [c_int] * 4 + [c_void_p] * 4 + [c_void_p]),
     "rg_cem_rollout_tiles": (c_int, [c_int, c_int]),
     "rg_cem_group": (c_int, [c_void_p, ctypes.c_uint64, c_int, c_int, c_int] + [c_void_p] * 3 + [c_void_p]),

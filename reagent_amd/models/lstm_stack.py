@@ -7,6 +7,8 @@ their state_dict keys stay rnn.weight_ih_l0 ...
   backward: per layer, from the top, rg_lstm_backward, dW_ih and db_ih = wgrad_rows(dgates, x), dW_hh and db_hh =
             wgrad_rows(dgates, [h0; h_all[:-1]]), dx = rg_fc_dgrad(dgates, W_ih); wgrad_rows is rg_fc_wgrad_rows on the
             row-major operands from WGRAD_ROWS_MIN rows on, two rg_transpose_cast and rg_fc_wgrad below
+  forward_ablate: an ablation sweep's V x B virtual rows: rg_lstm_forward_ablate on layer 0's shared projection, then
+            forward's launches for the layers above
 
 A layer's initial hidden state is row k of an [L, B, H] tensor (MDNRNN's `hidden`) or one [B, H] tensor that every layer
 starts from (Seq2RewardNetwork's embedding); its initial cell is row k of an [L, B, H] tensor or zero.
@@ -111,6 +113,25 @@ def forward(rnn, x, T, B, H, layers, h0=None, c0=None, save=False):
         tape["x"].append(x), tape["h"].append(h_all), tape["c"].append(c_all), tape["gates"].append(gates)
         x = h_all.view(N, H)
     return tape
+
+
+def forward_ablate(rnn, x, xproj, T, B, H, layers, blocks, fill, fill_stride, max_width):
+    """the stack over the V x B virtual rows of an ablation sweep (V = blocks.shape[0]; see rg_lstm_forward_ablate) from a
+    zero state, saving nothing -> the top layer's h_all [T, V * B, H].  x [T * B, In] and xproj [T * B, 4H] = layer 0's
+    projection of the unablated rows, shared by all variants; the layers above are forward's launches with V * B as the batch"""
+    V = blocks.shape[0]
+    f = dict(dtype=F32, device=x.device)
+    w_ih, w_hh, _, b_hh = (p.detach() for p in layer_params(rnn, 0))
+    h_all, c_all = torch.empty(T, V * B, H, **f), torch.empty(T, V * B, H, **f)
+    ops.lstm_forward_ablate(xproj.view(T, B, 4 * H), x, w_ih, w_hh, b_hh, blocks, fill, fill_stride, max_width,
+                            h_all, c_all)
+    for k in range(1, layers):
+        w_ih, w_hh, b_ih, b_hh = (p.detach() for p in layer_params(rnn, k))
+        xp = torch.empty(T * V * B, 4 * H, **f)
+        ops.fc_forward(h_all.view(T * V * B, H), w_ih, b_ih, LINEAR, L.PREC_F32, y32=xp)
+        h_all, c_all = torch.empty(T, V * B, H, **f), torch.empty(T, V * B, H, **f)
+        ops.lstm_forward(xp.view(T, V * B, 4 * H), w_hh, b_hh, None, None, h_all, c_all)
+    return h_all
 
 
 def backward(rnn, tape, dh_top, grad, h0, c0, transposed_weight, want_dh0):

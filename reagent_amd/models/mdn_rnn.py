@@ -24,6 +24,10 @@ from .lstm_stack import _f32c, _Parameters
 
 F32 = torch.float32
 LINEAR = L.ACT["linear"]
+# device memory one chunk of an ablation sweep's variants may take (MDNRNN.ablation_losses), at least one variant per
+# chunk; a variant is T * B * sweep_floats_per_row() floats (most of it gmm_linear's output).  The losses do not depend on
+# the chunking: a row's bits depend on that row alone in every launch of the sweep
+SWEEP_WORKSPACE_BYTES = 1 << 30
 
 
 class MDNRNN(nn.Module):
@@ -96,6 +100,41 @@ class MDNRNN(nn.Module):
         sigmas, logpi = torch.empty(N, G, S, **f), torch.empty(N, G, **f)
         ops.mdn_outputs(tape["z"], G, S, sigmas, logpi)
         return self._split(tape, sigmas, logpi)
+
+    # ---- the ablation sweep ------------------------------------------------------------------------------------------
+    def ablation_losses(self, actions, states, next_state, reward, not_terminal, blocks, fill, fill_stride, max_width, weights,
+                        divide_by_state_dim, first_row):
+        """the head's four losses of every variant of an ablation sweep -> losses [V, 4] on the device, nothing saved.
+        Variant v replaces columns blocks[v] = (start, end) of cat([actions, states], -1) by fill[v * fill_stride + c] (see
+        rg_lstm_forward_ablate); next_state [T * B, S], reward, not_terminal [T * B] are the unablated batch's.  The passes:
+        one rg_fc_forward for layer 0's projection of the unablated rows, then per chunk of variants (as many as fit
+        SWEEP_WORKSPACE_BYTES) rg_lstm_forward_ablate, the layers above and gmm_linear over T * V * B rows, rg_wm_mdn_losses."""
+        dev = self.gmm_linear.weight.device
+        T, B = actions.shape[0], actions.shape[1]
+        N, H, V = T * B, self.num_hiddens, blocks.shape[0]
+        f = dict(dtype=F32, device=dev)
+        x = _f32c(torch.cat([actions.to(dev).float(), states.to(dev).float()], dim=-1)).view(N, -1)
+        assert x.shape[1] == self.action_dim + self.state_dim
+        w_ih, _, b_ih, _ = (p.detach() for p in lstm_stack.layer_params(self.rnn, 0))
+        xproj = torch.empty(N, 4 * H, **f)
+        ops.fc_forward(x, w_ih, b_ih, LINEAR, L.PREC_F32, y32=xproj)
+        gw, gb = self.gmm_linear.weight.detach(), self.gmm_linear.bias.detach()
+        chunk = max(1, SWEEP_WORKSPACE_BYTES // (4 * N * self.sweep_floats_per_row()))
+        losses = torch.empty(V, 4, **f)
+        flat = fill.view(-1)
+        for v0 in range(0, V, chunk):
+            n = min(chunk, V - v0)
+            top = lstm_stack.forward_ablate(self.rnn, x, xproj, T, B, H, self.num_hidden_layers, blocks[v0:v0 + n],
+                                            flat[v0 * fill_stride:], fill_stride, max_width)
+            z = torch.empty(N * n, gw.shape[0], **f)
+            ops.fc_forward(top.view(N * n, H), gw, gb, LINEAR, L.PREC_F32, y32=z)
+            ops.wm_mdn_losses(z, next_state, reward, not_terminal, T, B, n, self.num_gaussians, weights, divide_by_state_dim,
+                              first_row, losses[v0:v0 + n])
+        return losses
+
+    def sweep_floats_per_row(self):
+        """floats ablation_losses allocates per virtual row: layer 0's h and c, a projection, h and c per layer above, z"""
+        return 2 * self.num_hiddens + 6 * self.num_hiddens * (self.num_hidden_layers - 1) + self.gmm_linear.weight.shape[0]
 
     def get_initial_hidden_state(self, batch_size=1):
         return (torch.zeros(self.num_hidden_layers, batch_size, self.num_hiddens),

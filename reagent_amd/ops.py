@@ -776,6 +776,85 @@ def mdn_gmm_nll(batch, mus, sigmas, logpi, nll):
                                         L.stream_ptr()))
 
 
+# ---- world model (the evaluators) -------------------------------------------------------------------------------
+def _wm_blocks(blocks, count=None):
+    """a table of blocks: int32 [count, 2] = (start, end), contiguous, on the device"""
+    assert blocks.dtype == torch.int32 and blocks.is_contiguous() and blocks.ndim == 2 and blocks.shape[1] == 2
+    assert blocks.shape[0] >= 1 and (count is None or blocks.shape[0] == count)
+    return blocks.shape[0]
+
+
+def wm_feature_fill(x, blocks, fill):
+    """fill [W] at the blocks' columns = the replacement value of every block over the rows x [N, W] (see
+    rg_wm_feature_fill): a single column's mean, a wider (one-hot) block's first-lower-median indicator"""
+    _chk_dev(x, blocks, fill)
+    N, W = x.shape
+    F = _wm_blocks(blocks)
+    assert x.dtype == F32 and N >= 1 and W >= 1
+    _f32_flat(fill, W)
+    _run("rg_wm_feature_fill", dict(N=N, W=W, F=F),
+         lambda: L.lib().rg_wm_feature_fill(L.ptr(x), _ld(x), N, W, L.ptr(blocks), F, L.ptr(fill), L.stream_ptr()))
+
+
+def lstm_forward_ablate(xproj, x, w_ih, w_hh, b_hh, blocks, fill, fill_stride: int, max_width: int, h_all, c_all):
+    """layer 0 over V x B virtual rows (see rg_lstm_forward_ablate): xproj [T, B, 4H] and x [T * B, In] of the unablated
+    rows, variant v = blocks[v] with the values fill[v * fill_stride + c] (fill [In] with fill_stride 0, else [V, fill_stride]
+    with every block's end <= fill_stride), from the zero state; h_all, c_all [T, V, B, H]"""
+    _chk_dev(xproj, x, w_ih, w_hh, b_hh, blocks, fill, h_all, c_all)
+    T, B, H4 = xproj.shape
+    H, In, V = H4 // 4, x.shape[1], _wm_blocks(blocks)
+    _lstm_check(T, B * V, H)
+    if max_width > L.WM_MAX_BLOCK:
+        raise NotImplementedError(f"lstm_forward_ablate: a block {max_width} columns wide is not supported "
+                                  f"(at most {L.WM_MAX_BLOCK})")
+    if V > 65535:
+        raise NotImplementedError(f"lstm_forward_ablate: {V} variants in one launch are not supported (at most 65535)")
+    assert H4 == 4 * H and w_hh.shape == (4 * H, H) and w_ih.shape == (4 * H, In) and x.shape[0] == T * B and x.dtype == F32
+    assert 0 <= max_width <= In and fill_stride >= 0 and fill.dtype == F32 and fill.is_contiguous()
+    assert fill.numel() >= (V * fill_stride if fill_stride else In)  # ([V, fill_stride] holds every block's end, or [In])
+    _f32_flat(xproj, T * B * 4 * H), _f32_flat(w_ih, 4 * H * In), _f32_flat(w_hh, 4 * H * H), _f32_flat(b_hh, 4 * H)
+    _f32_flat(h_all, T * V * B * H), _f32_flat(c_all, T * V * B * H)
+    _run("rg_lstm_forward_ablate", dict(T=T, B=B, H=H, V=V, width=int(max_width)),
+         lambda: L.lib().rg_lstm_forward_ablate(L.ptr(xproj), L.ptr(x), _ld(x), L.ptr(w_ih), L.ptr(w_hh), L.ptr(b_hh),
+                                                L.ptr(blocks), L.ptr(fill), int(fill_stride),
+                                                int(max_width), T, B, H, In, V, L.ptr(h_all), L.ptr(c_all), L.stream_ptr()))
+
+
+def wm_mdn_losses(z, next_state, reward, not_terminal, T: int, B: int, V: int, num_gaussians: int, weights,
+                  divide_by_state_dim: bool, first_row: int, losses):
+    """losses [V, 4] = rg_mdn_head's gmm, bce, mse, loss of every variant (see rg_wm_mdn_losses): z [T * V * B, (2S + 1) G
+    + 2] with row (t, v, b), the unreplicated targets next_state [T * B, S], reward, not_terminal [T * B]"""
+    _chk_dev(z, next_state, reward, not_terminal, losses)
+    N, S = next_state.shape
+    G = int(num_gaussians)
+    _mdn_check(G, S)
+    _lstm_check(T, B * V, 1)
+    assert N == T * B and z.dtype == F32 and z.shape == (N * V, (2 * S + 1) * G + 2) and 0 <= first_row < N and V <= 65535
+    _f32_flat(next_state, N * S), _f32_flat(reward, N), _f32_flat(not_terminal, N), _f32_flat(losses, 4 * V)
+    partials = torch.empty(3 * int(L.lib().rg_wm_mdn_losses_partials(T, B, V)), dtype=torch.float64, device=z.device)
+    w = [float(x) for x in weights]
+    _run("rg_wm_mdn_losses", dict(T=T, B=B, V=V, G=G, S=S),
+         lambda: L.lib().rg_wm_mdn_losses(L.ptr(z), _ld(z), L.ptr(next_state), L.ptr(reward), L.ptr(not_terminal), w[0], w[1],
+                                          w[2], int(bool(divide_by_state_dim)), int(first_row), T, B, V, G, S,
+                                          L.ptr(partials), L.ptr(losses), L.stream_ptr()))
+
+
+def wm_mus_sensitivity(z, z_shuffled, num_gaussians: int, state_dim: int, blocks, sensitivity):
+    """sensitivity [F] = mean over rows and gaussians of sum_{c in block f} |mus_shuffled - mus|, the mus read as the first
+    G * S columns of the two gmm_linear outputs z, z_shuffled [N, .] (see rg_wm_mus_sensitivity)"""
+    _chk_dev(z, z_shuffled, blocks, sensitivity)
+    N, G, S = z.shape[0], int(num_gaussians), int(state_dim)
+    F = _wm_blocks(blocks)
+    _mdn_check(G, S)
+    assert z.dtype == z_shuffled.dtype == F32 and z.shape == z_shuffled.shape and z.shape[1] >= G * S and F <= 65535
+    assert _ld(z) == _ld(z_shuffled)
+    _f32_flat(sensitivity, F)
+    partials = torch.empty(int(L.lib().rg_wm_mus_sensitivity_partials(N, F)), dtype=torch.float64, device=z.device)
+    _run("rg_wm_mus_sensitivity", dict(N=N, G=G, S=S, F=F),
+         lambda: L.lib().rg_wm_mus_sensitivity(L.ptr(z), L.ptr(z_shuffled), _ld(z), N, G, S, L.ptr(blocks), F,
+                                               L.ptr(partials), L.ptr(sensitivity), L.stream_ptr()))
+
+
 # ---- world model (Seq2Reward) -----------------------------------------------------------------------------------
 def lstm_fanout_step(h_prev, c_prev, proj, from_table: bool, w_hh, b_hh, fanout: int, h, c):
     """one LSTM layer's single step over the parents * fanout children of a prefix-tree level (see rg_lstm_fanout_step): child
