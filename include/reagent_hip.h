@@ -506,6 +506,19 @@ int rg_replay_dqn_batch(const rg_replay_view* view, const int64_t* indices, int 
 int rg_replay_dqn_batch_pooled(const rg_replay_view* view, const int64_t* index_pool, const int64_t* cursor,
                                double* pre_tick_sched, int batch, const rg_norm_col* cols, const float* quantiles,
                                const rg_dqn_batch_out* out, rg_stream_t stream);
+/* The bf16 mirror of the observation column (same ABI number: new entry points, no layout moved).  In offline training the
+ * store and the normalization table stay put, so pack_bf16(Preprocessor.forward(observation[row])) is the same value at every
+ * draw of a row: rg_replay_mirror_build makes it once per stored row, mirror [capacity, n_features] bf16 (16-byte aligned),
+ * rows row_begin <= r < row_end (the whole store in one launch, or the slice an add wrote), bit for bit what
+ * rg_replay_dqn_batch writes into `state` for index r with the same cols / quantiles and state_dtype RG_DT_BF16.
+ * rg_replay_dqn_batch_mirror is rg_replay_dqn_batch (cursor NULL: `indices` [batch]) or rg_replay_dqn_batch_pooled (cursor
+ * given: `indices` is the index pool, pre_tick_sched as there) with the state / next_state rows copied from the mirror:
+ * view->observation is not read, out->state_dtype must be RG_DT_BF16, every output equals the other entry points' bit for bit.
+ * RG_EUNSUPPORTED as for rg_replay_dqn_batch. */
+int rg_replay_mirror_build(const float* observation, int64_t capacity, int64_t row_begin, int64_t row_end, int n_features,
+                           const rg_norm_col* cols, const float* quantiles, void* mirror, rg_stream_t stream);
+int rg_replay_dqn_batch_mirror(const rg_replay_view* view, const void* mirror, const int64_t* indices, const int64_t* cursor,
+                               double* pre_tick_sched, int batch, const rg_dqn_batch_out* out, rg_stream_t stream);
 
 /* ABI 11.  The continuous-action twin of rg_replay_dqn_batch: ReplayBuffer.sample_transition_batch
  * (reagent/replay_memory/circular_replay_buffer.py:614-706, stack_size 1, dense fp32 observations and [capacity, action_dim]

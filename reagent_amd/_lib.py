@@ -266,6 +266,9 @@ SIGNATURES = {
                                         ctypes.POINTER(PolicyBatchOut), c_void_p]),
     "rg_replay_dqn_batch_pooled": (c_int, [ctypes.POINTER(ReplayView), c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p,
                                             ctypes.POINTER(DqnBatchOut), c_void_p]),
+    "rg_replay_mirror_build": (c_int, [c_void_p, c_i64, c_i64, c_i64, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "rg_replay_dqn_batch_mirror": (c_int, [ctypes.POINTER(ReplayView), c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                            ctypes.POINTER(DqnBatchOut), c_void_p]),
     "rg_table_check_actions": (c_int, [ctypes.POINTER(DqnTable), c_void_p, c_int, c_void_p, c_void_p]),
     "rg_tile_concat": (c_int, [c_void_p, c_i64, c_void_p, c_i64, c_int, c_int, c_int, c_int, c_void_p, c_i64, c_void_p]),
     "rg_pdqn_head_partials": (c_int, [c_int]),

@@ -304,6 +304,65 @@ __global__ void make_policy_input_kernel(const float* __restrict__ action, long 
 // next-state rows can be fetched in the launch that finds them, and the one-hot / not_terminal /
 // exp(log_prob) work of make_dqn_input_kernel reads the store directly.  Same arithmetic, operation
 // for operation, as the three kernels it replaces (tests compare them bit for bit).
+
+// The column descriptors as the row pieces read them.  Round 5: the descriptors of the four columns of a 16-byte chunk come
+// out of LDS as three 16-byte reads of a structure-of-arrays image (op | p0 | p1; p2 / p3 only for the two ops that have them)
+// instead of twelve 4-byte reads of 24-byte records at a lane stride of 96 bytes — an 8-way bank conflict each: PMC
+// (profiles/r04_pmc) showed the LDS pipe busy for half of the launch, 74 % of those cycles conflicts.
+__device__ __forceinline__ void stage_norm_cols(const rg_norm_col* __restrict__ cols, int F, int* s_op, float* s_p0, float* s_p1,
+                                                float* s_p2, float* s_p3) {
+  for (int j = threadIdx.x; j < F; j += blockDim.x) {
+    const rg_norm_col c = cols[j];
+    s_op[j] = c.op; s_p0[j] = c.p0; s_p1[j] = c.p1; s_p2[j] = c.p2; s_p3[j] = c.p3;
+  }
+}
+
+// Preprocessor.forward (all present) on the four features of chunk `ch`.  ONE body for the sampler's row pieces and for
+// replay_mirror_build_kernel: a mirror row holds the bits the sampler would make of the stored row.
+__device__ __forceinline__ void normalize_chunk(const int* s_op, const float* s_p0, const float* s_p1, const float* s_p2,
+                                                const float* s_p3, int ch, float (&w)[4], const float* __restrict__ quantiles) {
+  typedef __attribute__((ext_vector_type(4))) int i32x4;
+  const i32x4 op = *(const i32x4*)(s_op + ch * 4);
+  const f32x4 p0 = *(const f32x4*)(s_p0 + ch * 4), p1 = *(const f32x4*)(s_p1 + ch * 4);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    rg_norm_col c;
+    c.op = op[e]; c.in_col = 0; c.p0 = p0[e]; c.p1 = p1[e]; c.p2 = 0.f; c.p3 = 0.f;
+    if (c.op == RG_NORM_BOXCOX || c.op == RG_NORM_CONTINUOUS_ACTION) {
+      c.p2 = s_p2[ch * 4 + e];
+      c.p3 = s_p3[ch * 4 + e];
+    }
+    w[e] = normalize_value(c, w[e], 1.f, quantiles);
+  }
+}
+
+// rows s_src[r] (-> state row r) and s_nxt[r] (-> next_state row r) of the bf16 mirror, r < nrows, in pieces of sizeof(V)
+// bytes: consecutive lanes take the pieces of a transition's state row and then of its next-state row — with update_horizon 1
+// the store neighbour, so the two rows are ONE contiguous stretch (512 bytes at F = 128) of one wave request.  Four streaming
+// loads in flight per thread, all issued before the first store (the vec16 loop of replay_gather_kernel).
+template <typename V>
+__device__ __forceinline__ void copy_mirror_rows(const bf16_t* __restrict__ mirror, const int64_t* s_src, const int64_t* s_nxt,
+                                                 int F, int nrows, bf16_t* __restrict__ state, bf16_t* __restrict__ next_state) {
+  constexpr int EPP = (int)(sizeof(V) / sizeof(bf16_t)), GU = 4;
+  const int ppr = F / EPP, ppt = 2 * ppr, total = nrows * ppt;
+  for (int it0 = threadIdx.x; it0 < total; it0 += blockDim.x * GU) {
+    V raw[GU];
+#pragma unroll
+    for (int u = 0; u < GU; ++u) {
+      const int it = it0 + u * blockDim.x < total ? it0 + u * (int)blockDim.x : total - 1;
+      const int r = it / ppt, p = it - r * ppt;
+      raw[u] = stream_load((const V*)(mirror + (p < ppr ? s_src[r] : s_nxt[r]) * F + (p < ppr ? p : p - ppr) * EPP));
+    }
+#pragma unroll
+    for (int u = 0; u < GU; ++u) {
+      const int it = it0 + u * blockDim.x;
+      if (it >= total) continue;
+      const int r = it / ppt, p = it - r * ppt;
+      *(V*)((p < ppr ? state : next_state) + (long)r * F + (p < ppr ? p : p - ppr) * EPP) = raw[u];
+    }
+  }
+}
+
 struct ReplayBatchArgs {
   rg_replay_view v;
   rg_dqn_batch_out o;
@@ -314,8 +373,14 @@ struct ReplayBatchArgs {
 // schedule (sched[0] += 1: nobody reads it between this launch and the step's update, which is then told that the count
 // already includes it — rg_mlp_update_desc.sched_pre_ticked).  The update launch advances the cursor in turn
 // (rg_mlp_update_desc.post_tick): a replayed step needs neither an index copy nor a tick launch of its own.
-__global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __restrict__ indices, int batch,
-                                        const rg_norm_col* __restrict__ cols, const float* __restrict__ quantiles,
+//
+// MIRROR (rg_replay_dqn_batch_mirror): the row pieces copy rows of `mirror` [capacity][F] bf16 — what replay_mirror_build_kernel
+// made of the observation rows with the same table, i.e. the very bits the other form writes for them — instead of reading
+// fp32 rows and normalizing them: half the row bytes in, no descriptor image in LDS, no arithmetic.  With update_horizon 1 the
+// two rows of a transition are neighbours in the mirror (one 512-byte stretch at F = 128).
+template <bool MIRROR>
+__global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const bf16_t* __restrict__ mirror, const int64_t* __restrict__ indices,
+                                        int batch, const rg_norm_col* __restrict__ cols, const float* __restrict__ quantiles,
                                         const int64_t* __restrict__ cursor, double* __restrict__ pre_tick) {
   if (cursor) indices += cursor[0] * (long)batch;
   if (pre_tick && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) pre_tick[0] = pre_tick[0] + 1.0;
@@ -333,7 +398,8 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
   // loads in flight per thread, the next-state row the store neighbour of the state row — and two independent row pieces
   // in flight per thread measured the same as this one-piece-per-thread loop: with eight waves per SIMD the launch is not
   // short of requests in flight, it runs at what random 512-byte rows get from the HBM.)
-  const int piece = blockIdx.y;  // 0 = state, 1 = next_state, 2 = everything else
+  // 0 = state, 1 = next_state, 2 = everything else; MIRROR: 0 = both row pieces (grid.y = 2)
+  const int piece = MIRROR && blockIdx.y == 1 ? 2 : blockIdx.y;
   const int F = v.n_features, A = v.n_actions, H = v.update_horizon;
   const int64_t C = v.capacity;
   // (idx + k) % C without the 64-bit division: idx < C and k <= H <= C
@@ -358,24 +424,21 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
       s_nact[threadIdx.x] = (a1 >= 0 && a1 < A) ? (int)a1 : -1;
     }
   }
-  // Round 5: the descriptors of the four columns of a 16-byte chunk come out of LDS as three 16-byte reads of a
-  // structure-of-arrays image (op | p0 | p1; p2 / p3 only for the two ops that have them) instead of twelve 4-byte reads of
-  // 24-byte records at a lane stride of 96 bytes — an 8-way bank conflict each: PMC (profiles/r04_pmc) showed the LDS pipe
-  // busy for half of the launch, 74 % of those cycles conflicts.  Same arithmetic, same bits.
   const int cpr = F >> 2;  // F % 4 == 0 (checked by the host)
   int* s_op = (int*)s_nc;                       // [GATHER_MAX_LDS_COLS] each, inside the same 12 KB
   float* s_p0 = (float*)s_nc + GATHER_MAX_LDS_COLS;
   float* s_p1 = s_p0 + GATHER_MAX_LDS_COLS;
   float* s_p2 = s_p1 + GATHER_MAX_LDS_COLS;
   float* s_p3 = s_p2 + GATHER_MAX_LDS_COLS;
-  if (piece < 2 && cols)
-    for (int j = threadIdx.x; j < F; j += blockDim.x) {
-      const rg_norm_col c = cols[j];
-      s_op[j] = c.op; s_p0[j] = c.p0; s_p1[j] = c.p1; s_p2[j] = c.p2; s_p3[j] = c.p3;
-    }
+  if (!MIRROR && piece < 2 && cols) stage_norm_cols(cols, F, s_op, s_p0, s_p1, s_p2, s_p3);
   __syncthreads();
+  if (MIRROR && piece < 2) {
+    bf16_t *st = (bf16_t*)o.state + (long)row0 * F, *nx = (bf16_t*)o.next_state + (long)row0 * F;
+    if ((F & 7) == 0) copy_mirror_rows<f32x4>(mirror, s_src, s_nxt, F, nrows, st, nx);
+    else copy_mirror_rows<f32x2>(mirror, s_src, s_nxt, F, nrows, st, nx);  // F % 4 == 0: rows of 8-byte pieces
+    return;
+  }
   if (piece < 2) {
-    typedef __attribute__((ext_vector_type(4))) int i32x4;
     void* dst = piece == 0 ? o.state : o.next_state;
     const int total = nrows * cpr;
     for (int it = threadIdx.x; it < total; it += blockDim.x) {
@@ -384,20 +447,7 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
       // weights out of L2 (same-box A/B with the streaming reduce loads: C2 step -2.8 %)
       const f32x4 raw = stream_load((const f32x4*)(v.observation + s_src[r] * F + ch * 4));
       float w[4] = {raw[0], raw[1], raw[2], raw[3]};
-      if (cols) {
-        const i32x4 op = *(const i32x4*)(s_op + ch * 4);
-        const f32x4 p0 = *(const f32x4*)(s_p0 + ch * 4), p1 = *(const f32x4*)(s_p1 + ch * 4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          rg_norm_col c;
-          c.op = op[e]; c.in_col = 0; c.p0 = p0[e]; c.p1 = p1[e]; c.p2 = 0.f; c.p3 = 0.f;
-          if (c.op == RG_NORM_BOXCOX || c.op == RG_NORM_CONTINUOUS_ACTION) {
-            c.p2 = s_p2[ch * 4 + e];
-            c.p3 = s_p3[ch * 4 + e];
-          }
-          w[e] = normalize_value(c, w[e], 1.f, quantiles);
-        }
-      }
+      if (cols) normalize_chunk(s_op, s_p0, s_p1, s_p2, s_p3, ch, w, quantiles);
       const long at = (long)(row0 + r) * F + ch * 4;
       if (o.state_dtype == RG_DT_BF16) {
         uint2 pk;
@@ -437,6 +487,37 @@ __global__ void replay_dqn_batch_kernel(ReplayBatchArgs a, const int64_t* __rest
     if (o.possible_actions_mask)
       o.possible_actions_mask[at] = v.possible_actions_mask ? v.possible_actions_mask[idx * A + k] : 1.f;
     o.possible_next_actions_mask[at] = v.possible_actions_mask ? v.possible_actions_mask[nidx * A + k] : 1.f;
+  }
+}
+
+// mirror[r, :] = pack_bf16(Preprocessor.forward(observation[r, :])) for the stored rows r0 <= r < r1: what the row pieces of
+// replay_dqn_batch_kernel<false> write for row r (normalize_chunk and pack_bf16x2 are theirs), made once per stored row
+// instead of once per draw.  A workgroup converts 64 consecutive rows; the whole store is one launch.
+__global__ void replay_mirror_build_kernel(const float* __restrict__ observation, int64_t r0, int64_t r1, int F,
+                                           const rg_norm_col* __restrict__ cols, const float* __restrict__ quantiles,
+                                           bf16_t* __restrict__ mirror) {
+  __shared__ __attribute__((aligned(16))) rg_norm_col s_nc[GATHER_MAX_LDS_COLS];
+  int* s_op = (int*)s_nc;
+  float* s_p0 = (float*)s_nc + GATHER_MAX_LDS_COLS;
+  float* s_p1 = s_p0 + GATHER_MAX_LDS_COLS;
+  float* s_p2 = s_p1 + GATHER_MAX_LDS_COLS;
+  float* s_p3 = s_p2 + GATHER_MAX_LDS_COLS;
+  stage_norm_cols(cols, F, s_op, s_p0, s_p1, s_p2, s_p3);
+  __syncthreads();
+  const int64_t row0 = r0 + (int64_t)blockIdx.x * GATHER_ROWS_PER_WG;
+  const int nrows = (r1 - row0 < GATHER_ROWS_PER_WG) ? (int)(r1 - row0) : GATHER_ROWS_PER_WG;
+  const int cpr = F >> 2;  // F % 4 == 0 (checked by the host)
+  const int total = nrows * cpr;
+  for (int it = threadIdx.x; it < total; it += blockDim.x) {
+    const int r = it / cpr, ch = it - r * cpr;
+    const long at = (long)(row0 + r) * F + ch * 4;
+    const f32x4 raw = stream_load((const f32x4*)(observation + at));
+    float w[4] = {raw[0], raw[1], raw[2], raw[3]};
+    normalize_chunk(s_op, s_p0, s_p1, s_p2, s_p3, ch, w, quantiles);
+    uint2 pk;
+    pk.x = pack_bf16x2(w[0], w[1]);
+    pk.y = pack_bf16x2(w[2], w[3]);
+    *(uint2*)(mirror + at) = pk;
   }
 }
 
@@ -604,40 +685,68 @@ int rg_replay_gather(const rg_gather_col* cols, int ncols, int64_t capacity, int
   return (int)hipGetLastError();
 }
 
-static int replay_dqn_batch_launch(const rg_replay_view* view, const int64_t* indices, int batch, const rg_norm_col* cols,
-                                   const float* quantiles, const rg_dqn_batch_out* out, const int64_t* cursor,
-                                   double* pre_tick, rg_stream_t stream) {
+// mirror != null: the rows come from the bf16 mirror of the observation column (cols / quantiles went into the mirror)
+static int replay_dqn_batch_launch(const rg_replay_view* view, const void* mirror, const int64_t* indices, int batch,
+                                   const rg_norm_col* cols, const float* quantiles, const rg_dqn_batch_out* out,
+                                   const int64_t* cursor, double* pre_tick, rg_stream_t stream) {
   if (!view || !out || batch < 0) return RG_EINVAL;
   if (batch == 0) return RG_OK;
   const rg_replay_view& v = *view;
   const rg_dqn_batch_out& o = *out;
-  if (!indices || !v.observation || !v.action || !v.reward || !v.terminal || !v.decays || v.capacity <= 0 ||
+  if (!indices || (!v.observation && !mirror) || !v.action || !v.reward || !v.terminal || !v.decays || v.capacity <= 0 ||
       v.n_features <= 0 || v.n_actions <= 0 || v.update_horizon <= 0)
     return RG_EINVAL;
   if (!o.state || !o.next_state || !o.action || !o.next_action || !o.reward || !o.not_terminal ||
       !o.possible_next_actions_mask)
     return RG_EINVAL;
   if (o.state_dtype != RG_DT_F32 && o.state_dtype != RG_DT_BF16) return RG_EINVAL;
-  if (!cols && o.state_dtype != RG_DT_F32) return RG_EINVAL;  // a raw copy stays fp32
-  if ((v.n_features & 3) || v.n_features > GATHER_MAX_LDS_COLS || (((uintptr_t)v.observation) & 15) ||
+  if (!cols && !mirror && o.state_dtype != RG_DT_F32) return RG_EINVAL;  // a raw copy stays fp32
+  if (mirror && o.state_dtype != RG_DT_BF16) return RG_EINVAL;           // the mirror holds bf16 rows
+  if ((v.n_features & 3) || v.n_features > GATHER_MAX_LDS_COLS || (((uintptr_t)(mirror ? mirror : v.observation)) & 15) ||
       (((uintptr_t)o.state) & 15) || (((uintptr_t)o.next_state) & 15))
     return RG_EUNSUPPORTED;  // callers fall back to rg_replay_nstep + rg_replay_gather + rg_make_dqn_input
   ReplayBatchArgs a{v, o};
-  RG_LAUNCH(replay_dqn_batch_kernel, dim3((batch + GATHER_ROWS_PER_WG - 1) / GATHER_ROWS_PER_WG, 3), dim3(256),
-            (hipStream_t)stream, a, indices, batch, cols, quantiles, cursor, pre_tick);
+  const dim3 grid((batch + GATHER_ROWS_PER_WG - 1) / GATHER_ROWS_PER_WG, mirror ? 2 : 3);
+  if (mirror)
+    RG_LAUNCH(replay_dqn_batch_kernel<true>, grid, dim3(256), (hipStream_t)stream, a, (const bf16_t*)mirror, indices, batch,
+              cols, quantiles, cursor, pre_tick);
+  else
+    RG_LAUNCH(replay_dqn_batch_kernel<false>, grid, dim3(256), (hipStream_t)stream, a, (const bf16_t*)nullptr, indices, batch,
+              cols, quantiles, cursor, pre_tick);
   return (int)hipGetLastError();
+}
+
+int rg_replay_mirror_build(const float* observation, int64_t capacity, int64_t row_begin, int64_t row_end, int n_features,
+                           const rg_norm_col* cols, const float* quantiles, void* mirror, rg_stream_t stream) {
+  if (!observation || !cols || !mirror || capacity <= 0 || n_features <= 0 || row_begin < 0 || row_end < row_begin ||
+      row_end > capacity)
+    return RG_EINVAL;
+  if ((n_features & 3) || n_features > GATHER_MAX_LDS_COLS || (((uintptr_t)observation) & 15) || (((uintptr_t)mirror) & 15))
+    return RG_EUNSUPPORTED;
+  if (row_end == row_begin) return RG_OK;
+  const int64_t blocks = (row_end - row_begin + GATHER_ROWS_PER_WG - 1) / GATHER_ROWS_PER_WG;
+  if (blocks > 0x7fffffff) return RG_EUNSUPPORTED;
+  RG_LAUNCH(replay_mirror_build_kernel, dim3((unsigned)blocks), dim3(256), (hipStream_t)stream, observation, row_begin, row_end,
+            n_features, cols, quantiles, (bf16_t*)mirror);
+  return (int)hipGetLastError();
+}
+
+int rg_replay_dqn_batch_mirror(const rg_replay_view* view, const void* mirror, const int64_t* indices, const int64_t* cursor,
+                               double* pre_tick_sched, int batch, const rg_dqn_batch_out* out, rg_stream_t stream) {
+  if (!mirror || (pre_tick_sched && !cursor)) return RG_EINVAL;
+  return replay_dqn_batch_launch(view, mirror, indices, batch, nullptr, nullptr, out, cursor, pre_tick_sched, stream);
 }
 
 int rg_replay_dqn_batch(const rg_replay_view* view, const int64_t* indices, int batch, const rg_norm_col* cols,
                         const float* quantiles, const rg_dqn_batch_out* out, rg_stream_t stream) {
-  return replay_dqn_batch_launch(view, indices, batch, cols, quantiles, out, nullptr, nullptr, stream);
+  return replay_dqn_batch_launch(view, nullptr, indices, batch, cols, quantiles, out, nullptr, nullptr, stream);
 }
 
 int rg_replay_dqn_batch_pooled(const rg_replay_view* view, const int64_t* index_pool, const int64_t* cursor,
                                double* pre_tick_sched, int batch, const rg_norm_col* cols, const float* quantiles,
                                const rg_dqn_batch_out* out, rg_stream_t stream) {
   if (!cursor) return RG_EINVAL;
-  return replay_dqn_batch_launch(view, index_pool, batch, cols, quantiles, out, cursor, pre_tick_sched, stream);
+  return replay_dqn_batch_launch(view, nullptr, index_pool, batch, cols, quantiles, out, cursor, pre_tick_sched, stream);
 }
 
 int rg_replay_policy_batch(const rg_policy_replay_view* view, const int64_t* indices, int batch, const rg_norm_col* cols,

@@ -423,14 +423,36 @@ class PooledIndices:
         return self.pool.shape[1]
 
 
-def replay_dqn_batch(view: "L.ReplayView", indices, cols_dev, quantiles, out: dict) -> bool:
-    """one-launch sample + input maker (+ normalize); False = shape not supported by the fused kernel"""
+def replay_mirror_build(observation, cols_dev, quantiles, mirror, row_begin: int, row_end: int) -> bool:
+    """mirror[r] = bf16(normalize(observation[r])) for row_begin <= r < row_end (rg_replay_mirror_build); False = the store
+    is not of the shape the kernel serves"""
+    _chk_dev(observation, cols_dev, quantiles, mirror)
+    C, F_ = observation.shape
+    assert observation.dtype == F32 and observation.is_contiguous()
+    assert mirror.dtype == BF16 and mirror.shape == observation.shape and mirror.is_contiguous()
+    rc = [0]
+
+    def call():
+        rc[0] = L.lib().rg_replay_mirror_build(L.ptr(observation), C, row_begin, row_end, F_, L.ptr(cols_dev), L.ptr(quantiles),
+                                               L.ptr(mirror), L.stream_ptr())
+        return 0 if rc[0] == L.EUNSUPPORTED else rc[0]
+
+    _run("rg_replay_mirror_build", dict(rows=row_end - row_begin, bytes_per_row=F_ * 6), call)
+    return rc[0] == 0
+
+
+def replay_dqn_batch(view: "L.ReplayView", indices, cols_dev, quantiles, out: dict, mirror=None) -> bool:
+    """one-launch sample + input maker (+ normalize); False = shape not supported by the fused kernel.
+    mirror (the store's rows already normalized, bf16: replay_mirror_build with the same cols_dev / quantiles): the state rows
+    are copied from it (rg_replay_dqn_batch_mirror), same outputs."""
     pooled = indices if isinstance(indices, PooledIndices) else None
     if pooled is not None:
-        _chk_dev(pooled.pool, pooled.cursor, pooled.sched, cols_dev, quantiles, *out.values())
+        _chk_dev(pooled.pool, pooled.cursor, pooled.sched, cols_dev, quantiles, mirror, *out.values())
     else:
-        _chk_dev(indices, cols_dev, quantiles, *out.values())
+        _chk_dev(indices, cols_dev, quantiles, mirror, *out.values())
         assert indices.dtype == torch.int64 and indices.is_contiguous()
+    assert mirror is None or (mirror.dtype == BF16 and mirror.is_contiguous()
+                              and tuple(mirror.shape) == (view.capacity, view.n_features) and out["state"].dtype == BF16)
     o = L.DqnBatchOut()
     for name in L.BATCH_OUT_FIELDS:
         t = out.get(name)
@@ -441,7 +463,12 @@ def replay_dqn_batch(view: "L.ReplayView", indices, cols_dev, quantiles, out: di
     rc = [0]
 
     def call():
-        if pooled is not None:
+        if mirror is not None:
+            rc[0] = L.lib().rg_replay_dqn_batch_mirror(
+                ctypes.byref(view), L.ptr(mirror), pooled.pool.data_ptr() if pooled is not None else L.ptr(indices),
+                pooled.cursor.data_ptr() if pooled is not None else None, L.ptr(pooled.sched) if pooled is not None else None,
+                B, ctypes.byref(o), L.stream_ptr())
+        elif pooled is not None:
             rc[0] = L.lib().rg_replay_dqn_batch_pooled(ctypes.byref(view), pooled.pool.data_ptr(), pooled.cursor.data_ptr(),
                                                        L.ptr(pooled.sched), B, L.ptr(cols_dev), L.ptr(quantiles),
                                                        ctypes.byref(o), L.stream_ptr())
@@ -452,9 +479,9 @@ def replay_dqn_batch(view: "L.ReplayView", indices, cols_dev, quantiles, out: di
 
     F_, A_, H_ = view.n_features, view.n_actions, view.update_horizon
     es = out["state"].element_size()
-    # algorithmic bytes per transition: rows in (2 F fp32) and out (2 F), n-step window, action / log_prob /
-    # index reads, masks in (if stored) and out, one-hots and scalars out
-    nbytes = (2 * F_ * 4 + 2 * F_ * es + 5 * H_ + 2 * 8 + 4 + 8 + (2 * A_ * 4 if view.possible_actions_mask else 0)
+    # algorithmic bytes per transition: rows in (2 F fp32, or bf16 from the mirror) and out (2 F), n-step window, action /
+    # log_prob / index reads, masks in (if stored) and out, one-hots and scalars out
+    nbytes = (2 * F_ * (4 if mirror is None else 2) + 2 * F_ * es + 5 * H_ + 2 * 8 + 4 + 8 + (2 * A_ * 4 if view.possible_actions_mask else 0)
               + 4 * A_ * 4 + 3 * 4)
     _run("rg_replay_dqn_batch", dict(B=B, bytes_per_row=nbytes), call)
     return rc[0] == 0

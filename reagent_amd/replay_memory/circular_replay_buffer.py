@@ -204,6 +204,7 @@ class ReplayBuffer:
             if k == "terminal":
                 arr = arr.astype(bool)
             self._store[k][cursor] = torch.from_numpy(arr)
+        self._mirror_wrote(cursor, 1)
         self._terminal_host[cursor] = bool(kwargs["terminal"])
         self.add_count += 1
 
@@ -252,6 +253,7 @@ class ReplayBuffer:
         for k, src in staged.items():
             col = self._store[k]
             col.index_copy_(0, pos_dev, src.to(device=col.device, dtype=col.dtype))
+        self._mirror_wrote(c0, T)
         # ---- validity (the rules of add, :491-522, for stack_size 1)
         # k[t]: transitions of t's episode before t;  at add t: valid[pos t] = False; if k[t] >= h: valid[pos t - h] = True;
         # at a terminal t: the last min(k[t] + 1, h) indices of the episode become valid.  An index ends up valid iff one
@@ -298,6 +300,7 @@ class ReplayBuffer:
             self.initialize_buffer(**first)
         for k, v in columns.items():
             self._store[k][:n].copy_(v.to(self._store[k].dtype))
+        self._mirror_wrote(0, n)
         term = columns["terminal"].cpu().numpy().astype(bool)
         self._terminal_host[:n] = term
         self.add_count = np.array(n)
@@ -317,6 +320,63 @@ class ReplayBuffer:
         self._valid_dirty = True
         ep_start = 0 if not len(np.flatnonzero(term)) else int(np.flatnonzero(term)[-1]) + 1
         self._num_transitions_in_current_episode = n - ep_start
+
+    # ---- the bf16 mirror of the observation column ------------------------------------------------
+    # pack_bf16(Preprocessor.forward(observation[row])) is the same value at every draw of a row while the row and the
+    # preprocessor's table stay put, which in offline training is always: sample_dqn_input's bf16 form therefore copies rows
+    # of a [capacity, F] bf16 mirror (rg_replay_mirror_build, once per stored row) instead of reading fp32 rows and normalizing
+    # them at every draw (rg_replay_dqn_batch_mirror: half the row bytes, same bits).  Derived data: capacity * F * 2 bytes of
+    # HBM beside the store, never checkpointed, rebuilt on demand; keyed to the table's two tensors; the rows an add wrote are
+    # rebuilt before the next sample.
+    _use_mirror = True  # False (set on the instance when the allocation fails): the sampler that normalizes at every draw
+    _mirror = None
+
+    def _mirror_wrote(self, start: int, count: int):
+        """the observation rows of slots start .. start + count (wrapping) were just rewritten through this class"""
+        m = self._mirror
+        if m is not None:
+            m["dirty"].append((int(start), int(count)))
+            m["obs_version"] = self._store["observation"]._version
+
+    def _bf16_mirror(self, pre) -> Optional[torch.Tensor]:
+        """the up-to-date mirror for `pre`'s table, or None = sample from the fp32 rows"""
+        if not self._use_mirror:
+            return None
+        obs, cols, q = self._store["observation"], pre._col_table, pre._quantiles
+        capturing = obs.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        table = (cols._version, q._version)
+        m = self._mirror
+        fresh = (m is not None and m["obs"] is obs and m["cols"] is cols and m["quantiles"] is q and m["table"] == table
+                 and m["obs_version"] == obs._version)  # (a write that did not come through add / add_many / load_columns moves it)
+        if fresh and not m["dirty"]:
+            pass
+        elif capturing:
+            return None  # a build must not become a node of the step's graph (capture()'s warm-up steps have made the mirror)
+        elif fresh and len(m["dirty"]) <= 16:
+            C = self._replay_capacity
+            for start, count in m["dirty"]:
+                for r0, r1 in ((start, min(start + count, C)), (0, start + count - C)):  # the slice, and its part past the wrap
+                    if r1 > r0:
+                        ops.replay_mirror_build(obs, cols, q, m["buf"], r0, r1)
+            m["dirty"] = []
+        else:
+            buf = m["buf"] if m is not None and m["buf"].shape == obs.shape and m["buf"].device == obs.device else None
+            self._mirror = m = None
+            try:
+                buf = buf if buf is not None else torch.empty(obs.shape, dtype=torch.bfloat16, device=obs.device)
+            except RuntimeError:  # out of memory: 2 bytes per stored feature that this device does not have
+                self._use_mirror = False
+                return None
+            if not ops.replay_mirror_build(obs, cols, q, buf, 0, self._replay_capacity):
+                return None  # not a store the kernels serve (the sampler will say the same)
+            self._mirror = m = dict(buf=buf, obs=obs, cols=cols, quantiles=q, table=table, obs_version=obs._version, dirty=[],
+                                    stream=None)
+        if obs.device.type == "cuda" and not capturing:
+            now = torch.cuda.current_stream(obs.device)
+            if m["stream"] not in (None, now):  # built or patched on one stream, read on another (the prefetching loop's)
+                now.wait_stream(m["stream"])
+            m["stream"] = now
+        return m["buf"]
 
     def is_empty(self) -> bool:
         return self.add_count == 0
@@ -473,7 +533,8 @@ class ReplayBuffer:
                          state_dtype=None):
         """sample_transition_batch + DiscreteDqnInputMaker (trainer_preprocessor.py:100-158) [+ the state
         Preprocessor] as ONE launch (rg_replay_dqn_batch): the n-step bookkeeping, both state gathers and
-        the one-hot / not_terminal / exp(log_prob) work, bit-identical to the three-launch path.  Returns
+        the one-hot / not_terminal / exp(log_prob) work, bit-identical to the three-launch path.  With a preprocessor
+        and state_dtype bf16 the state rows are copied from the buffer's bf16 mirror (`_bf16_mirror`), same bits.  Returns
         None when the store is not of the shape the fused kernel serves (stacked frames, non-fp32 or
         non-vector observations, an ENUM-expanding preprocessor, ...): callers then use the generic path."""
         from ..core import types as rlt
@@ -522,8 +583,9 @@ class ReplayBuffer:
                    not_terminal=torch.empty(B, 1, **f32), possible_actions_mask=torch.empty(B, A, **f32),
                    possible_next_actions_mask=torch.empty(B, A, **f32), action_probability=torch.empty(B, 1, **f32))
         pre = state_preprocessor
+        mirror = self._bf16_mirror(pre) if pre is not None and sdt == torch.bfloat16 else None
         if not ops.replay_dqn_batch(view, indices, pre._col_table if pre is not None else None,
-                                    pre._quantiles if pre is not None else None, out):
+                                    pre._quantiles if pre is not None else None, out, mirror=mirror):
             return None
         return rlt.DiscreteDqnInput(
             state=rlt.FeatureData(float_features=out["state"]), action=out["action"],
