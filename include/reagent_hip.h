@@ -1798,6 +1798,62 @@ size_t rg_fc_wgrad_rows_workspace_bytes(int out_features, int in_features, int r
 int rg_fc_wgrad_rows(const float* dz, int64_t ld_dz, const float* x, int64_t ldx, float* dw, float* db, void* workspace,
                      size_t workspace_bytes, int out_features, int in_features, int rows, rg_stream_t stream);
 
+/* ---- feature importance by perturbation of an FC Q-network (feature_importance.hip) ----------------------------------------
+ * Replaces the loop of reagent/evaluation/feature_importance/feature_importance_perturbation.py:36-61, which per feature
+ * deep-copies the batch, permutes one raw column and its presence over the rows, runs the preprocessor and the whole network
+ * again and reads one scalar back: F + 1 forwards and F host reads.  After the preprocessor, permuting raw feature f changes
+ * only f's block of normalized columns, so variant v = (perm[v], blocks[v]) of the batch is never written: layer 0 of row
+ * (v, b) is the SHARED pre-activation z0[b] = x[b] W0^T + b0 (rg_fc_forward, RG_ACT_LINEAR, RG_PREC_F32) plus the correction
+ * sum_{c in block v} (x[perm[v, b], c] - x[b, c]) * W0[., c], and everything above layer 0 stays in LDS.  Additive symbols:
+ * the ABI number does not move.  All fp32; no atomics: two runs give the same bits.
+ *
+ * rg_fi_sweep: grid (ceil(batch / 32), variants), a workgroup (4 waves) per 32-row tile of one variant.  (32 rows, not 64:
+ * the two k-major activation images of a 512-wide stack are 2 x 64 KB at 32 rows, which with the weight slab is 145 KB of
+ * the CU's 160 KB; 64 rows would need 256 KB.)  x [batch, dims[0]] (pitch ldx) = the normalized batch; z0 [batch, dims[1]]
+ * (pitch ldz0); perm int32 [variants, batch], row b of variant v reads row perm[v, b] (clamped into the batch); blocks int32
+ * [variants, 2] = (start, end) into dims[0]; the table is read on the device only, so no call checks it: the kernel cuts a
+ * block to the row and to its first max_width columns (max_width sizes the delta image; the caller passes the widest block's
+ * width, or gets the truncated variant); empty is legal; net: the stack, weights w[l] contiguous
+ * [dims[l + 1], dims[l]] (nn.Linear layout), bias[l] [dims[l + 1]] or NULL, acts[l] an RG_ACT_* code; q [batch, A] (pitch
+ * ldq) = the base prediction, A = dims[n_layers]; mask [batch, A] (pitch ldmask), RG_FI_MASKED only.
+ *   correction   a block below 32 columns: one fmaf chain per element in ascending c from +0; 32 columns or more: the
+ *                fp32-input MFMA chain in ascending c over the deltas staged k-major in LDS.  Then h0 = act0(z0 + correction).
+ *   layers 1..   rg_fc_forward's RG_PREC_F32 arithmetic: v_mfma_f32_32x32x2_f32 chains in ascending k from +0 over the
+ *                pairs (2i, 2i + 1), + bias, the activation; the weights pass through LDS in slabs of 8 k shared by the four
+ *                waves (a wave owns the 32-column tiles wave, wave + 4, ...); two activation images, ping-pong.
+ *   prediction   RG_FI_MAX: max_a; RG_FI_MASKED: sum_a mask[b, a] * q[b, a] in double in ascending a; RG_FI_PER_ACTION: the A
+ *                values.  The base prediction is formed from q the same way.
+ *   partials     [variants, tiles, C] doubles (C = A under RG_FI_PER_ACTION, else 1): the tile's sum of |pred_v - pred_base|
+ *                in double in ascending row order; rows past the batch add exactly 0.
+ * Nothing of size variants x batch is written.
+ * rg_fi_finish: importance[v, c] = fp32((sum of v's partials in ascending tile order) / batch), [variants, C] contiguous.
+ * rg_fi_partials: the doubles rg_fi_sweep writes (variants * ceil(batch / 32) * C); 0 for anything the calls refuse.
+ *
+ * Contracts: trip counts depend on the dims and the block widths alone; a row's bits depend on that row and its permuted
+ * partner alone; a variant whose perm is the identity or whose block is empty gives importance == 0.0 exactly when q is the
+ * stack's rg_fc_forward RG_PREC_F32 output on z0's x (the correction is an exact +0 and the rest is that path's arithmetic
+ * on the same z0).
+ * RG_EINVAL for a null pointer not marked nullable, a size below 1, a pitch below its row, n_layers outside 1 ..
+ * RG_FI_MAX_LAYERS, an unknown act or reduce code; RG_EUNSUPPORTED for dims[l] > RG_FI_MAX_WIDTH (l >= 1), A >
+ * RG_FI_MAX_ACTIONS, dims[0] > RG_FI_MAX_INPUT, max_width > RG_FI_MAX_WIDTH, more than 65535 variants. */
+#define RG_FI_MAX_LAYERS 8
+#define RG_FI_MAX_WIDTH 512
+#define RG_FI_MAX_ACTIONS 64
+#define RG_FI_MAX_INPUT 4096
+enum { RG_FI_MAX = 0, RG_FI_MASKED = 1, RG_FI_PER_ACTION = 2 };
+typedef struct rg_fi_net {
+  int32_t n_layers;
+  int32_t dims[RG_FI_MAX_LAYERS + 1]; /* dims[0] = normalized input columns, dims[l + 1] = out of layer l */
+  int32_t acts[RG_FI_MAX_LAYERS];
+  const float* w[RG_FI_MAX_LAYERS];
+  const float* bias[RG_FI_MAX_LAYERS];
+} rg_fi_net;
+int rg_fi_partials(int batch, int variants, int actions, int reduce);
+int rg_fi_sweep(const rg_fi_net* net /* host */, const float* x, int64_t ldx, const float* z0, int64_t ldz0, const int32_t* perm,
+                const int32_t* blocks, const float* q, int64_t ldq, const float* mask, int64_t ldmask, int reduce, int max_width,
+                int batch, int variants, double* partials, rg_stream_t stream);
+int rg_fi_finish(const double* partials, int batch, int variants, int columns, float* importance, rg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -78,6 +78,20 @@ class NormCol(ctypes.Structure):
 
 BBB_MAX_SEGMENTS, BBB_CHUNK = 16, 1024  # RG_BBB_MAX_SEGMENTS, RG_BBB_CHUNK
 
+FI_MAX_LAYERS, FI_MAX_WIDTH, FI_MAX_ACTIONS, FI_MAX_INPUT = 8, 512, 64, 4096  # RG_FI_MAX_*: rg_fi_sweep's limits
+FI_REDUCE = {"max_q": 0, "logged_action": 1, "per_action": 2}  # RG_FI_MAX, RG_FI_MASKED, RG_FI_PER_ACTION
+
+
+class FiNet(ctypes.Structure):
+    """rg_fi_net: the stack rg_fi_sweep runs (host memory; the pointers are device memory)"""
+    _fields_ = [
+        ("n_layers", ctypes.c_int32),
+        ("dims", ctypes.c_int32 * (FI_MAX_LAYERS + 1)),
+        ("acts", ctypes.c_int32 * FI_MAX_LAYERS),
+        ("w", c_void_p * FI_MAX_LAYERS),
+        ("bias", c_void_p * FI_MAX_LAYERS),
+    ]
+
 
 class BbbSegment(ctypes.Structure):
     _fields_ = [("mu", c_void_p), ("rho", c_void_p), ("w", c_void_p), ("eps", c_void_p), ("dw", c_void_p), ("dmu", c_void_p),
@@ -432,6 +446,10 @@ SIGNATURES = {
     "rg_seqconv_wgrad": (c_int, [c_void_p, c_i64] * 3 + [c_int] * 7 + [c_i64, c_i64, c_void_p, c_void_p, c_void_p, c_sz, c_void_p]),
     "rg_ngram_window": (c_int, [c_void_p, c_i64] + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
     "rg_ngram_window_backward": (c_int, [c_void_p, c_i64] * 2 + [c_int] * 4 + [c_void_p, c_i64, c_void_p]),
+    "rg_fi_partials": (c_int, [c_int] * 4),
+    "rg_fi_sweep": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_i64]
+                    + [c_int] * 4 + [c_void_p, c_void_p]),
+    "rg_fi_finish": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p, c_void_p]),
 }
 
 _lib = None

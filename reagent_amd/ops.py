@@ -882,6 +882,62 @@ def wm_mus_sensitivity(z, z_shuffled, num_gaussians: int, state_dim: int, blocks
                                                L.ptr(partials), L.ptr(sensitivity), L.stream_ptr()))
 
 
+# ---- feature importance by perturbation ---------------------------------------------------------------------------
+def fi_partials(batch: int, variants: int, actions: int, reduce: int) -> int:
+    return int(L.lib().rg_fi_partials(batch, variants, actions, reduce))
+
+
+def fi_sweep(x, z0, perm, blocks, weights, biases, acts, q, mask, reduce: int, max_width: int, partials):
+    """partials = the tile sums of |pred_v - pred_base| of every variant v = (perm[v], blocks[v]) of the normalized batch x
+    [B, D] (see rg_fi_sweep): z0 [B, H1] = layer 0's pre-activation of x, weights / biases / acts the stack's layers (RG_ACT_*
+    codes; a bias may be None), q [B, A] its output on x, mask [B, A] with reduce RG_FI_MASKED; perm int32 [V, B], blocks
+    int32 [V, 2], max_width >= every block's width"""
+    _chk_dev(x, z0, perm, blocks, q, mask, partials, *weights, *biases)
+    B, D = x.shape
+    V, n = _wm_blocks(blocks), len(weights)
+    dims = [D] + [w.shape[0] for w in weights]
+    if not 1 <= n <= L.FI_MAX_LAYERS:
+        raise NotImplementedError(f"fi_sweep: a stack of {n} layers is not supported (1 .. {L.FI_MAX_LAYERS})")
+    if max(dims[1:]) > L.FI_MAX_WIDTH:
+        raise NotImplementedError(f"fi_sweep: a layer {max(dims[1:])} wide is not supported (at most {L.FI_MAX_WIDTH})")
+    if dims[-1] > L.FI_MAX_ACTIONS:
+        raise NotImplementedError(f"fi_sweep: {dims[-1]} actions are not supported (at most {L.FI_MAX_ACTIONS})")
+    if D > L.FI_MAX_INPUT or max_width > L.FI_MAX_WIDTH:
+        raise NotImplementedError(f"fi_sweep: {D} input columns / a block {max_width} columns wide are not supported (at most "
+                                  f"{L.FI_MAX_INPUT} / {L.FI_MAX_WIDTH})")
+    if V > 65535:
+        raise NotImplementedError(f"fi_sweep: {V} variants in one launch are not supported (at most 65535)")
+    assert len(biases) == len(acts) == n and x.dtype == z0.dtype == q.dtype == F32
+    assert z0.shape == (B, dims[1]) and q.shape == (B, dims[-1]) and 0 <= max_width <= D
+    assert perm.dtype == torch.int32 and perm.is_contiguous() and perm.shape == (V, B)
+    assert (mask is not None and mask.dtype == F32 and mask.shape == q.shape) or reduce != L.FI_REDUCE["logged_action"]
+    net = L.FiNet()
+    net.n_layers = n
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        _f32_flat(w, dims[l + 1] * dims[l]), _f32_flat(b, dims[l + 1])
+        net.w[l], net.bias[l], net.acts[l] = L.ptr(w), L.ptr(b), int(acts[l])
+    for l, d in enumerate(dims):
+        net.dims[l] = d
+    assert partials.dtype == torch.float64 and partials.is_contiguous()
+    assert partials.numel() >= fi_partials(B, V, dims[-1], reduce) > 0
+    _run("rg_fi_sweep", dict(B=B, V=V, dims=tuple(dims), width=int(max_width), reduce=int(reduce)),
+         lambda: L.lib().rg_fi_sweep(ctypes.byref(net), L.ptr(x), _ld(x), L.ptr(z0), _ld(z0), L.ptr(perm), L.ptr(blocks), L.ptr(q),
+                                     _ld(q), L.ptr(mask), _ld(mask) if mask is not None else 0, int(reduce), int(max_width), B,
+                                     V, L.ptr(partials), L.stream_ptr()))
+
+
+def fi_finish(partials, batch: int, importance):
+    """importance [V] or [V, A] = the variants' partials added in tile order, / batch, rounded once (see rg_fi_finish)"""
+    _chk_dev(partials, importance)
+    V = importance.shape[0]
+    C = importance.shape[1] if importance.ndim == 2 else 1
+    _f32_flat(importance, V * C)
+    assert partials.dtype == torch.float64 and partials.is_contiguous()
+    assert partials.numel() >= V * ((batch + 31) // 32) * C
+    _run("rg_fi_finish", dict(B=batch, V=V, C=C),
+         lambda: L.lib().rg_fi_finish(L.ptr(partials), int(batch), V, C, L.ptr(importance), L.stream_ptr()))
+
+
 # ---- world model (Seq2Reward) -----------------------------------------------------------------------------------
 def lstm_fanout_step(h_prev, c_prev, proj, from_table: bool, w_hh, b_hh, fanout: int, h, c):
     """one LSTM layer's single step over the parents * fanout children of a prefix-tree level (see rg_lstm_fanout_step): child

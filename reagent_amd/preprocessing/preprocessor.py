@@ -71,6 +71,16 @@ class Preprocessor(Module):
         q = torch.tensor(quantiles if quantiles else [0.0], dtype=torch.float32)
         self.register_buffer("_quantiles", q.to(self.device), persistent=False)
 
+    def column_blocks(self) -> List[Tuple[int, int]]:
+        """per input column (sorted_features order): its (start, end) block of output columns, read from the op-code table
+        (one column per feature, an ENUM's len(possible_values))"""
+        table = (L.NormCol * self.num_output_features).from_buffer_copy(self._col_table.cpu().numpy().tobytes())
+        blocks = [[None, None] for _ in self.sorted_features]
+        for out_col, c in enumerate(table):
+            b = blocks[c.in_col]
+            b[0], b[1] = out_col if b[0] is None else b[0], out_col + 1
+        return [(b[0], b[1]) if b[0] is not None else (0, 0) for b in blocks]  # (an ENUM without values has no column)
+
     def input_prototype(self) -> Tuple[torch.Tensor, torch.Tensor]:
         n = len(self.normalization_parameters)
         return (torch.randn(1, n, device=self.device),
